@@ -2,7 +2,14 @@
 """Decode throughput of the MI355X paged-attention INT8 decoder (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|c1]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs (--dump-outputs) and prints the result line.  Everything that takes
+runs of its own (the attention roofline, the CPU baseline, the gather timed
+alone and the extra weak-scaling run at N > 1) is measured only under --full;
+a plain line carries null in those fields.
 
 Workload (default, BASELINE config C3): INT8Decoder with 24 layers, 16 heads,
 head_dim 128 (hidden 2048, inter 8192, vocab 50257), a batch of 64 sequences,
@@ -23,11 +30,20 @@ definition) and C4 scale weak.  At N > 1 a strong line also carries the weak
 figure (the config's batch on EVERY rank) as `weak_scaling`.  value = tokens/s
 of the whole job = rows of all ranks / t_step, t_step = max over ranks.
 
-Also reported (one JSON line on rank 0):
+Also reported under --full (one JSON line on rank 0):
   roofline     the paged-attention launch (the dominant kernel), timed live with
                HIP events on the stream it runs on, against 8 TB/s HBM
   cpu_baseline the oracle's restated INT8Decoder step on this host's cores
                (bounded sample, see `sample`)
+
+--dump-outputs DIR (rank 0, after the timed steps): what the timed loop hands
+its caller in its last step, as float32 DIR/<name>.npy.  One GPU: `next_ids`,
+the greedy ids of every row (the single-GPU loop asks the step for no logits),
+and `logits_next_step`, the [rows][V] logits of ONE further, untimed step fed
+by those ids (every layer, the KV the timed steps appended and the LM head
+feed it, so two builds can be compared beyond an argmax).  N > 1: the rows
+rank 0 gathered in the last timed step (`logits` or `next_ids`, --gather).
+The inputs depend on the arguments alone (seeded), not on the run.
 """
 from __future__ import annotations
 
@@ -420,12 +436,49 @@ class StubStep:
         out.copy_(torch.from_numpy(self.next.astype(np.int32)))
 
 
-def run_mode(cfg, args, world, rank, strong, backend, stub):
+DUMP_ARRAY_BYTES = 60 << 20  # --dump-outputs: every file together stays under 64 MB
+
+
+def save_output(out_dir, name, t):
+    """DIR/<name>.npy, float32.  An array over DUMP_ARRAY_BYTES is cut to a
+    fixed (seed 0) sorted sample of its rows, listed in DIR/<name>_rows.npy."""
+    a = np.ascontiguousarray(t.detach().to("cpu").numpy(), dtype=np.float32)
+    if a.nbytes > DUMP_ARRAY_BYTES:
+        keep = max(1, DUMP_ARRAY_BYTES // (a.nbytes // a.shape[0]))
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        a = a[rows]
+        np.save(out_dir / f"{name}_rows.npy", rows.astype(np.float64))
+    np.save(out_dir / f"{name}.npy", a)
+
+
+def dump_outputs(sd, rows, vocab, device, sync, out_dir):
+    """--dump-outputs, straight after the timed steps (see the module docstring)."""
+    import torch
+    out_dir = Path(out_dir)
+    if sd.g is not None:  # N > 1: the last timed step's gathered rows, on rank 0 alone
+        if sd.rank == 0:
+            out_dir.mkdir(parents=True, exist_ok=True)
+            last = sd.g.recv[sd.g.slot ^ 1]
+            save_output(out_dir, "logits" if sd.gather == "logits" else "next_ids",
+                        torch.cat([last[r][:n] for r, n in enumerate(sd.g.rows)]))
+        return
+    out_dir.mkdir(parents=True, exist_ok=True)
+    ids = torch.empty((rows,), dtype=torch.int32, device=device)
+    sd.step_fn.ids_into(ids)
+    logits = torch.empty((rows, vocab), dtype=torch.float32, device=device)
+    sd.step_fn(None, logits)
+    sync()
+    save_output(out_dir, "next_ids", ids)
+    save_output(out_dir, "logits_next_step", logits)
+
+
+def run_mode(cfg, args, world, rank, strong, backend, stub, dump=None):
     """Build this rank's decoder for one scaling mode and time the sharded
     decode loop (dist_decode.ShardedDecode + timed_run).  strong: the global
     batch (args.global_batch or the config's batch) split over the ranks,
     first tokens one global draw, sharded; weak: the config's batch on every
-    rank, first tokens drawn per rank.  Returns (stats, decoder or None)."""
+    rank, first tokens drawn per rank.  dump: --dump-outputs' directory.
+    Returns (stats, decoder or None)."""
     import dist_decode
     B, T = cfg["B"], cfg["T"]
     shard_rows, G = None, B * world
@@ -479,7 +532,11 @@ def run_mode(cfg, args, world, rank, strong, backend, stub):
     st = {"rows_this_rank": B, "global_rows": G, "t_step": t_step,
           "per_rank_ms_per_step": [round(t / args.steps * 1e3, 4) for t in rank_times],
           "step_times": step_times, "value": G / t_step}
-    t_g = dist_decode.time_gather(sd, sync=sync, timer_device=timer) if world > 1 else None
+    if dump:
+        dump_outputs(sd, B, cfg["V"], device, sync, dump)
+    t_g = None
+    if world > 1 and args.full:
+        t_g = dist_decode.time_gather(sd, sync=sync, timer_device=timer)
     if t_g is not None:
         per_peer = sd.g.bufs[0].numel() * sd.g.bufs[0].element_size()
         st["gather"] = {"what": gather, "bytes_per_rank": per_peer,
@@ -496,6 +553,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the attention roofline, the "
+                         "CPU baseline and, at N > 1, the gather alone and the weak-scaling run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=20.0)
@@ -573,15 +635,15 @@ def main():
     if mode == "auto":
         mode = "strong" if (cfg.get("strong") or args.global_batch) else "weak"
     strong = mode == "strong" and "beams" not in cfg
-    st, dec = run_mode(cfg, args, world, rank, strong, backend, stub)
+    st, dec = run_mode(cfg, args, world, rank, strong, backend, stub, dump=args.dump_outputs)
     B, T, t_step = st["rows_this_rank"], cfg["T"], st["t_step"]
     T_mean = T + args.warmup + args.steps / 2.0
     host_gather = world > 1 and backend != "nccl"
 
     # roofline of the dominant kernel (paged attention): the step's own launch,
-    # timed live on rank 0's decoder
+    # timed live on rank 0's decoder (--full)
     roof, step_b = None, step_bytes(cfg, T_mean, B)
-    if dec is not None and rank == 0:
+    if dec is not None and rank == 0 and args.full:
         T_now = dec.context_len(0)
         nsplit, form = dec.attention_plan()
         t_attn = time_attention(dec, cfg["L"])
@@ -615,7 +677,7 @@ def main():
             roof["ungrouped_launch_us"] = round(t_plain * 1e6, 2)  # plain schedule, fp32 out
 
     weak = None
-    if world > 1 and strong and not args.no_weak_extra:
+    if world > 1 and strong and args.full and not args.no_weak_extra:
         del dec  # the strong run's pools go before the weak run allocates its own
         import gc
         gc.collect()
@@ -632,7 +694,7 @@ def main():
     del dec
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.config, args.cpu_budget)
         except Exception as ex:  # the baseline never blocks the GPU number

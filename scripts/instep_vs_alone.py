@@ -1,7 +1,8 @@
 """The paged-attention launch inside the decode step against the same launch
 run on its own (bench.py's time_attention: llm_decoder_run_attention of layer
 0, 3 warm-up + 20 timed launches after the timed steps), from one rocprofv3
-run of bench.py: kernel durations (--kernel-trace) and per-dispatch counters
+run of bench.py --full (scripts/trace_step.sh NAME --full; a plain run has no
+standalone launches): kernel durations (--kernel-trace) and per-dispatch counters
 (--pmc passes).  The last ALONE attention dispatches of the run are the
 standalone ones, the earlier ones are in-step.
 

@@ -12,6 +12,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -35,8 +36,8 @@ def _line(r):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_launcher_starts_n_ranks_strong_headline(n):
-    res = _line(_bench("--gpus", str(n), "--stub-step", "--no-cpu-baseline", "--steps", "3",
-                       "--warmup", "1"))
+    res = _line(_bench("--gpus", str(n), "--stub-step", "--full", "--no-cpu-baseline",
+                       "--steps", "3", "--warmup", "1"))
     assert res["n_gpus"] == n
     assert res["process_group"] == {"backend": "gloo", "size": n}
     assert len(res["per_rank_ms_per_step"]) == n
@@ -58,15 +59,64 @@ def test_launcher_starts_n_ranks_strong_headline(n):
 
 def test_launcher_weak_config_and_ids_gather():
     res = _line(_bench("--gpus", "2", "--config", "c5", "--gather", "ids", "--stub-step",
-                       "--no-cpu-baseline", "--steps", "2", "--warmup", "1"))
+                       "--full", "--no-cpu-baseline", "--steps", "2", "--warmup", "1"))
     assert res["n_gpus"] == 2 and res["scaling"] == "weak"
     assert res["config"]["global_batch"] == 128 and res["config"]["batch_per_gpu"] == 64
     assert res["gather"]["bytes_per_rank"] == 64 * 4
     assert res["weak_scaling"] is None
 
 
+def _stub_ids(tokens, steps, vocab=50257):
+    """StubStep's next ids after `steps` steps from `tokens`."""
+    t = np.asarray(tokens, np.int64)
+    for _ in range(steps):
+        t = (t * 31 + 7) % vocab
+    return t
+
+
+def test_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) measures the headline alone: the fields of what
+    takes runs of its own are null.  --dump-outputs writes the last timed
+    step's greedy ids -- exactly warmup + steps steps after the seeded first
+    tokens, so --steps really sets the number of timed steps -- and the logits
+    of the one further step they feed, float32."""
+    res = _line(_bench("--gpus", "1", "--stub-step", "--steps", "3", "--warmup", "2",
+                       "--dump-outputs", str(tmp_path / "out")))
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["ms_per_step"] > 0
+    assert res["value"] > 0 and res["unit"] == "tokens/s" and res["higher_is_better"] is True
+    assert res["roofline"] is None and res["cpu_baseline"] is None
+    assert res["weak_scaling"] is None and res["gather"] is None
+    first = np.random.default_rng(1234).integers(0, 50257, 64).astype(np.int32)
+    ids = np.load(tmp_path / "out" / "next_ids.npy")
+    assert ids.dtype == np.float32
+    np.testing.assert_array_equal(ids, _stub_ids(first, 5))
+    lg = np.load(tmp_path / "out" / "logits_next_step.npy")
+    assert lg.dtype == np.float32 and lg.shape == (64, 50257)
+    want = (_stub_ids(first, 5)[:, None] * 31 + np.arange(50257)[None, :] * 7) % 97
+    np.testing.assert_array_equal(lg, want)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["logits_next_step.npy",
+                                                                    "next_ids.npy"]
+
+
+def test_plain_run_at_n2_dumps_the_gathered_rows(tmp_path):
+    """N > 1, plain: no gather timed alone, no weak-scaling run; rank 0 dumps
+    the rows it gathered in the last timed step (ragged strong shards of 8 and
+    7 rows, in rank order)."""
+    res = _line(_bench("--gpus", "2", "--stub-step", "--global-batch", "15", "--steps", "2",
+                       "--warmup", "1", "--dump-outputs", str(tmp_path / "out")))
+    assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 15
+    assert res["gather"] is None and res["weak_scaling"] is None
+    assert res["roofline"] is None and res["cpu_baseline"] is None
+    first = np.random.default_rng(1234).integers(0, 50257, 15).astype(np.int32)
+    lg = np.load(tmp_path / "out" / "logits.npy")
+    assert lg.dtype == np.float32 and lg.shape == (15, 50257)
+    # the last timed step (the 3rd) was fed the ids of 2 steps
+    want = (_stub_ids(first, 2)[:, None] * 31 + np.arange(50257)[None, :] * 7) % 97
+    np.testing.assert_array_equal(lg, want)
+
+
 def test_launcher_cpu_baseline_on_rank0_at_n2():
-    res = _line(_bench("--gpus", "2", "--config", "c1", "--stub-step", "--steps", "2",
+    res = _line(_bench("--gpus", "2", "--config", "c1", "--stub-step", "--full", "--steps", "2",
                        "--warmup", "1", "--cpu-budget", "2"))
     assert res["n_gpus"] == 2
     cpu = res["cpu_baseline"]
@@ -102,7 +152,8 @@ def test_torchrun_launch_and_cpu_baseline_share():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         str(port), str(ROOT / "bench.py"), "--gpus", "2", "--config", "c1",
-                        "--stub-step", "--steps", "2", "--warmup", "1", "--cpu-budget", "2"],
+                        "--stub-step", "--full", "--steps", "2", "--warmup", "1", "--cpu-budget",
+                        "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     res = _line(r)
     assert res["n_gpus"] == 2 and res["process_group"]["size"] == 2
