@@ -34,14 +34,30 @@ enum llm_status {
                                first llm_decoder_sync or synchronous step after it */
 };
 
-/* Element types.  KV pools may be any of the four (the T of
+/* Element types.  KV pools may be any of the four of the reference (the T of
  * AttentionCUDA::forward, attention/attention_cuda.cu:58-94: __half, bf16,
- * int8_t (raw values, no scale), float); weights are LLM_I8 or LLM_F16. */
-enum llm_dtype { LLM_F16 = 0, LLM_I8 = 1, LLM_F32 = 2, LLM_BF16 = 3 };
+ * int8_t (raw values, no scale), float) or LLM_FP8; weights are LLM_I8 or
+ * LLM_F16.
+ * LLM_FP8 is OCP e4m3fn (bias 7, max +-448, no infinities, NaN = 0x7F / 0xFF:
+ * the gfx950 hardware format, not MI300's fnuz), one byte per element:
+ *   store: byte = cvt_e4m3_rne(clamp(y * (1 / scale), -448, +448)), NaN -> NaN
+ *   load:  value = decode(byte) * scale
+ * pa_decode / pa_decode_grouped / pa_decode_ex read LLM_FP8 pools as plain
+ * numbers (scale 1), as they read LLM_I8: a caller with scales folds K's into
+ * sm_scale and multiplies `out` by V's.  The decoder keeps one k_scale and one
+ * v_scale per layer (llm_decoder_set_kv_scales). */
+enum llm_dtype { LLM_F16 = 0, LLM_I8 = 1, LLM_F32 = 2, LLM_BF16 = 3, LLM_FP8 = 4 };
 enum llm_act { LLM_ACT_NONE = 0, LLM_ACT_RELU = 1, LLM_ACT_GELU = 2 };
 
 const char* llm_last_error(void);
 int llm_abi_version(void);
+
+/* Host-only codec of LLM_FP8 with the semantics above (plain C++, no device
+ * call): out[i] = encode(x[i] / scale) and out[i] = decode(in[i]) * scale.
+ * scale must be finite and > 0; values beyond +-448 * scale saturate to
+ * 0x7E / 0xFE; a NaN encodes to 0x7F (0xFF with the sign bit set). */
+int llm_fp8_e4m3_encode(const float* x, size_t n, float scale, uint8_t* out);
+int llm_fp8_e4m3_decode(const uint8_t* in, size_t n, float scale, float* out);
 
 /* ------------------------------------------------------------------------ */
 /* Paged decode attention                                                    */
@@ -65,7 +81,7 @@ typedef struct pa_kv_view {
   int32_t num_beams;
   int32_t num_heads;
   int32_t max_tiles;
-  int32_t kv_dtype;           /* LLM_F16 (default), LLM_BF16, LLM_F32 or LLM_I8; one page
+  int32_t kv_dtype;           /* LLM_F16 (default), LLM_BF16, LLM_F32, LLM_I8 or LLM_FP8; one page
                                * (page_size * head_dim elements) must be 1..16 KiB */
   int64_t page_stride;        /* bytes from page p to page p + 1 within each pool; 0 = one
                                * page (dense pools).  kv_cache's own pools interleave K and
@@ -277,7 +293,10 @@ typedef struct kv_cache kv_cache;
 int kv_cache_create(int num_layers, int num_beams, int num_heads, int head_dim, int page_size,
                     int max_tiles, long long num_pages, kv_cache** out);
 /* kv_cache_create with pools of kv_dtype elements (KVTileCache<T>,
- * kv_cache/kv_tile_cache.hpp:9 with T in {__half, bf16, int8_t, float}). */
+ * kv_cache/kv_tile_cache.hpp:9 with T in {__half, bf16, int8_t, float}, or
+ * LLM_FP8: one byte per element; kv_cache_write_tokens takes the raw bytes, and
+ * no file written from the cache holds scales -- the caller keeps them, as the
+ * reference's pool dumps keep no page table). */
 int kv_cache_create_typed(int num_layers, int num_beams, int num_heads, int head_dim,
                           int page_size, int max_tiles, long long num_pages, int kv_dtype,
                           kv_cache** out);
@@ -377,6 +396,24 @@ typedef struct llm_decoder_config {
 } llm_decoder_config;
 
 int llm_decoder_create(const llm_decoder_config* cfg, llm_decoder** out);
+/* llm_decoder_create with KV pools of kv_dtype: LLM_F16 (identical to
+ * llm_decoder_create) or LLM_FP8 (the qkv projection appends e4m3 bytes, the
+ * attention reads them; the default num_pages is the same number of pages, so
+ * the pool is half the bytes).  Any other element type is LLM_ERR_UNSUPPORTED,
+ * an unknown one LLM_ERR_INVALID, decided before any device allocation.
+ * Prompt chunks of an LLM_FP8 decoder run their attention through the decode
+ * kernel (pa_prefill reads fp16 pools only). */
+int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype, llm_decoder** out);
+/* Per-layer scales of an LLM_FP8 decoder: host arrays [num_layers], NULL = all
+ * 1.0 (the default), every value finite and > 0.  Allowed only while no rows
+ * are active (before begin_* / generate / prefill), else LLM_ERR_INVALID; on
+ * an fp16-KV decoder LLM_ERR_INVALID.  k_scale is folded into the attention's
+ * score multiplier and v_scale multiplies the normalised attention output
+ * once per (row, head), before anything downstream rounds it.  Scales are
+ * stored in no file. */
+int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale, const float* v_scale);
+/* LLM_F16 or LLM_FP8. */
+int llm_decoder_kv_dtype(const llm_decoder* d);
 void llm_decoder_destroy(llm_decoder* d);
 
 /* Host weights (row-major reference layouts), uploaded and packed on device.
@@ -438,7 +475,9 @@ int llm_decoder_set_sampling(llm_decoder* d, float temperature, int top_k, float
 /* Low-level stepping (bench / multi-GPU driver). */
 /* Start `batch` rows whose first context_len tokens are synthetic: every page
  * is allocated (shuffled order when shuffle != 0) and filled with seeded
- * random fp16 K/V on device. */
+ * random fp16 K/V on device (LLM_FP8 decoders: the same seeded values encoded
+ * at scale 1, whatever the layers' scales -- the pool bytes depend on the
+ * seed only, and a layer reads them times its scales). */
 int llm_decoder_begin_synthetic(llm_decoder* d, int batch, int context_len, uint64_t seed,
                                 int shuffle);
 /* Start num_seqs * beam_width rows (row = seq * beam_width + beam) for beam

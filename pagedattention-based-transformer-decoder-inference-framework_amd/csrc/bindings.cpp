@@ -12,6 +12,8 @@
 //   generate(input_ids, output_ids, max_gen_len, temperature=1.0)   (api/router.py:23,
 //       web/app.py:23, cli/chat_cli.py:24 — fills output_ids in place)
 // and both return / fill prompt + generated ids (cuda_decoder.cu:49,59).
+// Both decoders take a keyword kv_dtype ("float16" by default; "fp8" /
+// "float8_e4m3fn": LLM_FP8 KV pages with per-layer scales, set_kv_scales).
 // Additions: generate_batch, set_weights (host numpy arrays), low-level
 // begin_synthetic / step for the bench, PageTable / KVTileCache classes with
 // the kv_cache/ API names (page_table.hpp:5-37, kv_tile_cache.hpp:9-41) and
@@ -57,13 +59,18 @@ class Decoder {
  public:
   Decoder(int weight_dtype, int num_layers, int num_heads, int head_dim, int hidden_dim,
           int vocab_size, int max_seq_len, int max_batch, int page_size, int inter_dim,
-          float attn_scale, long long num_pages) {
+          float attn_scale, long long num_pages, const std::string& kv_dtype) {
+    const int kvt = kv_dtype == "float16" || kv_dtype == "half" || kv_dtype == "fp16" ? LLM_F16
+                    : kv_dtype == "fp8" || kv_dtype == "float8_e4m3fn"                  ? LLM_FP8
+                                                                                        : -1;
+    if (kvt < 0)
+      throw std::invalid_argument("kv_dtype must be 'float16' or 'fp8' / 'float8_e4m3fn'");
     llm_decoder_config c{};
     c.num_layers = num_layers; c.num_heads = num_heads; c.head_dim = head_dim;
     c.hidden_dim = hidden_dim; c.vocab_size = vocab_size; c.max_seq_len = max_seq_len;
     c.inter_dim = inter_dim; c.page_size = page_size; c.weight_dtype = weight_dtype;
     c.max_batch = max_batch; c.attn_scale = attn_scale; c.num_pages = num_pages;
-    check(llm_decoder_create(&c, &d_));
+    check(llm_decoder_create_kv(&c, kvt, &d_));
     cfg_ = c;
     if (cfg_.inter_dim <= 0) cfg_.inter_dim = 4 * hidden_dim;
   }
@@ -245,6 +252,20 @@ class Decoder {
     return py::make_tuple(ns, form);
   }
   uintptr_t kv_handle() const { return reinterpret_cast<uintptr_t>(llm_decoder_kv(d_)); }
+  // llm_decoder_set_kv_scales: per-layer scales of an fp8 KV decoder (None: all 1.0)
+  void set_kv_scales(py::object k, py::object v) {
+    std::vector<float> ks, vs;
+    if (!k.is_none()) ks = k.cast<std::vector<float>>();
+    if (!v.is_none()) vs = v.cast<std::vector<float>>();
+    if ((!k.is_none() && (int)ks.size() != cfg_.num_layers) ||
+        (!v.is_none() && (int)vs.size() != cfg_.num_layers))
+      throw std::invalid_argument("set_kv_scales: need one scale per layer");
+    check(llm_decoder_set_kv_scales(d_, k.is_none() ? nullptr : ks.data(),
+                                    v.is_none() ? nullptr : vs.data()));
+  }
+  std::string kv_dtype() const {
+    return llm_decoder_kv_dtype(d_) == LLM_FP8 ? "float8_e4m3fn" : "float16";
+  }
   const llm_decoder_config& config() const { return cfg_; }
 
  private:
@@ -255,15 +276,17 @@ class Decoder {
 class CUDADecoder : public Decoder {
  public:
   CUDADecoder(int L, int H, int D, int hid, int V, int S, int max_batch, int page_size, int inter,
-              float attn_scale, long long num_pages)
-      : Decoder(LLM_F16, L, H, D, hid, V, S, max_batch, page_size, inter, attn_scale, num_pages) {}
+              float attn_scale, long long num_pages, const std::string& kv_dtype)
+      : Decoder(LLM_F16, L, H, D, hid, V, S, max_batch, page_size, inter, attn_scale, num_pages,
+                kv_dtype) {}
 };
 
 class INT8Decoder : public Decoder {
  public:
   INT8Decoder(int L, int H, int D, int hid, int V, int S, int max_batch, int page_size, int inter,
-              float attn_scale, long long num_pages)
-      : Decoder(LLM_I8, L, H, D, hid, V, S, max_batch, page_size, inter, attn_scale, num_pages) {}
+              float attn_scale, long long num_pages, const std::string& kv_dtype)
+      : Decoder(LLM_I8, L, H, D, hid, V, S, max_batch, page_size, inter, attn_scale, num_pages,
+                kv_dtype) {}
 };
 
 // KVTileCache<T> (kv_cache/kv_tile_cache.hpp:9-41) with a layer dimension.
@@ -271,21 +294,24 @@ class KVTileCache {
  public:
   KVTileCache() = default;
   ~KVTileCache() { if (c_) kv_cache_destroy(c_); }
-  // dtype: the T of KVTileCache<T> — "float16" (default), "bfloat16", "float32", "int8"
+  // dtype: the T of KVTileCache<T> — "float16" (default), "bfloat16", "float32", "int8" --
+  // or "fp8" / "float8_e4m3fn" (LLM_FP8 bytes; the caller keeps the scales)
   void init(int num_pages, int tile_size, int head_dim, int num_layers, int num_beams,
             int num_heads, int max_tiles, const std::string& dtype) {
     const int kvt = dtype == "float16" || dtype == "half" ? LLM_F16
                     : dtype == "bfloat16"                 ? LLM_BF16
                     : dtype == "float32" || dtype == "float" ? LLM_F32
                     : dtype == "int8"                     ? LLM_I8
+                    : dtype == "fp8" || dtype == "float8_e4m3fn" ? LLM_FP8
                                                           : -1;
-    if (kvt < 0) throw std::invalid_argument("KVTileCache: dtype must be float16, bfloat16, float32 or int8");
+    if (kvt < 0)
+      throw std::invalid_argument("KVTileCache: dtype must be float16, bfloat16, float32, int8 or fp8");
     if (c_) { kv_cache_destroy(c_); c_ = nullptr; }
     check(kv_cache_create_typed(num_layers, num_beams, num_heads, head_dim, tile_size, max_tiles,
                                 num_pages, kvt, &c_));
     tile_size_ = tile_size; head_dim_ = head_dim; layers_ = num_layers; beams_ = num_beams;
     heads_ = num_heads; max_tiles_ = max_tiles; dtype_ = dtype;
-    es_ = kvt == LLM_F32 ? 4 : kvt == LLM_I8 ? 1 : 2;
+    es_ = kvt == LLM_F32 ? 4 : kvt == LLM_I8 || kvt == LLM_FP8 ? 1 : 2;
   }
   void resize(int new_num_pages, int new_tile_size) {  // kv_tile_cache.cpp:26-37: drops contents
     init(new_num_pages, new_tile_size, head_dim_, layers_, beams_, heads_, max_tiles_, dtype_);
@@ -427,10 +453,11 @@ PYBIND11_MODULE(llm_decoder, m) {
 
   auto dec_init = [](auto* cls) {
     return py::init([](int L, int H, int D, int hid, int V, int S, int max_batch, int page_size,
-                       int inter, float attn_scale, long long num_pages) {
+                       int inter, float attn_scale, long long num_pages,
+                       const std::string& kv_dtype) {
              return new std::remove_pointer_t<decltype(cls)>(L, H, D, hid, V, S, max_batch,
                                                              page_size, inter, attn_scale,
-                                                             num_pages);
+                                                             num_pages, kv_dtype);
            });
   };
   auto common = [&](auto& c) {
@@ -457,6 +484,9 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("oproj_status", &Decoder::oproj_status)
         .def("run_attention", &Decoder::run_attention, py::arg("layer") = 0,
              py::arg("stream") = 0)
+        .def("set_kv_scales", &Decoder::set_kv_scales, py::arg("k_scale") = py::none(),
+             py::arg("v_scale") = py::none())
+        .def_property_readonly("kv_dtype", &Decoder::kv_dtype)
         .def_property_readonly("kv_handle", &Decoder::kv_handle);
   };
   py::class_<Decoder>(m, "_Decoder");
@@ -464,13 +494,15 @@ PYBIND11_MODULE(llm_decoder, m) {
   cd.def(dec_init((CUDADecoder*)nullptr), py::arg("num_layers"), py::arg("num_heads"),
          py::arg("head_dim"), py::arg("hidden_dim"), py::arg("vocab_size"),
          py::arg("max_seq_len"), py::arg("max_batch") = 1, py::arg("page_size") = 16,
-         py::arg("inter_dim") = 0, py::arg("attn_scale") = 1.0f, py::arg("num_pages") = 0);
+         py::arg("inter_dim") = 0, py::arg("attn_scale") = 1.0f, py::arg("num_pages") = 0,
+         py::arg("kv_dtype") = "float16");
   common(cd);
   py::class_<INT8Decoder, Decoder> id(m, "INT8Decoder");
   id.def(dec_init((INT8Decoder*)nullptr), py::arg("num_layers"), py::arg("num_heads"),
          py::arg("head_dim"), py::arg("hidden_dim"), py::arg("vocab_size"),
          py::arg("max_seq_len"), py::arg("max_batch") = 1, py::arg("page_size") = 16,
-         py::arg("inter_dim") = 0, py::arg("attn_scale") = 1.0f, py::arg("num_pages") = 0);
+         py::arg("inter_dim") = 0, py::arg("attn_scale") = 1.0f, py::arg("num_pages") = 0,
+         py::arg("kv_dtype") = "float16");
   common(id);
   id.def("load_quantized_weights", &Decoder::load_quantized_weights)
       .def("quantize_weights", &Decoder::quantize_weights);

@@ -18,6 +18,7 @@
 // page every page_size tokens, copy-on-write of forked pages) happens on the
 // host between replays and is pushed with kv_cache_sync().
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -84,8 +85,12 @@ struct llm_decoder {
   bool weights_ready = false;
   int w_keep = 0;  // the GEMM weights fit the Infinity Cache: keep them there (w_keep_for)
 
-  // KV
+  // KV: fp16 pools, or LLM_FP8 bytes (csrc/fp8.hpp) with one K and one V
+  // scale per layer (llm_decoder_set_kv_scales; host copies: the step graph
+  // carries them as kernel arguments and is re-captured when they change)
   kv_cache* kv = nullptr;
+  int kvt = LLM_F16;
+  std::vector<float> k_scale, v_scale;
 
   // activations / state
   DevBuf<float> x, qkv, o, h1, logits, sa;
@@ -184,8 +189,12 @@ static int check_cfg(const llm_decoder_config& c) {
   return LLM_OK;
 }
 
-extern "C" int llm_decoder_create(const llm_decoder_config* cfg_in, llm_decoder** out) {
+static int create_decoder(const llm_decoder_config* cfg_in, int kv_dtype, llm_decoder** out) {
   LLM_REQUIRE(cfg_in && out, "llm_decoder_create: NULL");
+  LLM_REQUIRE(kv_elem_size(kv_dtype) > 0, "llm_decoder_create_kv: unknown kv_dtype");
+  if (kv_dtype != LLM_F16 && kv_dtype != LLM_FP8)
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_create_kv: the decoder's KV pools are LLM_F16 "
+                                     "or LLM_FP8");
   llm_decoder_config c = *cfg_in;
   if (c.inter_dim <= 0) c.inter_dim = 4 * c.hidden_dim;
   if (c.page_size <= 0) c.page_size = 16;
@@ -205,7 +214,11 @@ extern "C" int llm_decoder_create(const llm_decoder_config* cfg_in, llm_decoder*
   LLM_HIP_RET(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
   long long pages = c.num_pages > 0 ? c.num_pages
                                      : (long long)d->maxB * d->L * d->H * d->max_tiles;
-  RET_IF(kv_cache_create(d->L, d->maxB, d->H, d->D, d->TS, d->max_tiles, pages, &d->kv));
+  d->kvt = kv_dtype;
+  d->k_scale.assign(d->L, 1.f);
+  d->v_scale.assign(d->L, 1.f);
+  RET_IF(kv_cache_create_typed(d->L, d->maxB, d->H, d->D, d->TS, d->max_tiles, pages, kv_dtype,
+                               &d->kv));
   const int B = d->maxB, hid = d->hid, inter = d->inter;
   RET_IF(d->x.alloc((size_t)B * hid));
   RET_IF(d->qkv.alloc((size_t)B * 3 * hid));
@@ -248,6 +261,36 @@ extern "C" int llm_decoder_create(const llm_decoder_config* cfg_in, llm_decoder*
   d->use_graph = env_int("LLM_GRAPH", 1) != 0;
   d->h_pos.assign(B, 0);
   *out = d.release();
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_create(const llm_decoder_config* cfg, llm_decoder** out) {
+  return create_decoder(cfg, LLM_F16, out);
+}
+
+extern "C" int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype,
+                                     llm_decoder** out) {
+  return create_decoder(cfg, kv_dtype, out);
+}
+
+extern "C" int llm_decoder_kv_dtype(const llm_decoder* d) { return d ? d->kvt : -1; }
+
+extern "C" int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale,
+                                         const float* v_scale) {
+  LLM_REQUIRE(d, "llm_decoder_set_kv_scales: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->kvt == LLM_FP8, "llm_decoder_set_kv_scales: the decoder's KV pools are not LLM_FP8");
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_kv_scales: rows are active (set the scales before "
+                             "begin_* / generate / prefill)");
+  for (const float* s : {k_scale, v_scale})
+    for (int l = 0; s && l < d->L; ++l)
+      LLM_REQUIRE(std::isfinite(s[l]) && s[l] > 0.f,
+                  "llm_decoder_set_kv_scales: every scale must be finite and > 0");
+  for (int l = 0; l < d->L; ++l) {
+    d->k_scale[l] = k_scale ? k_scale[l] : 1.f;
+    d->v_scale[l] = v_scale ? v_scale[l] : 1.f;
+  }
+  d->graph_batch = -1;  // the step graph carries the scales as kernel arguments
   return LLM_OK;
 }
 
@@ -442,7 +485,10 @@ int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R) {
   app.num_pages = view.num_pages;
   app.H = H;
   app.D = D;
-  app.page_stride = (size_t)view.page_stride / sizeof(_Float16);
+  app.page_stride = (size_t)view.page_stride / kv_elem_size(kvt);
+  app.kv_dtype = kvt;
+  app.k_inv_scale = 1.0f / k_scale[l];
+  app.v_inv_scale = 1.0f / v_scale[l];
   WeightGemm g;
   g.dtype = wdtype;
   g.a_packed = 1;
@@ -500,7 +546,8 @@ bool llm_decoder::quant_prologue(const Rows& R) const {
 // Needs the workgroup-merge form (2..8 splits), head_dim <= 128 and <= 64
 // heads; otherwise the o_proj GEMM runs as before.
 bool llm_decoder::oproj_fusable(const Rows& R) {
-  if (wdtype != LLM_F16 || R.prefill_row >= 0 || R.row_group != 1 || R.beam_rows || !wo_heads.p ||
+  if (wdtype != LLM_F16 || kvt != LLM_F16 || R.prefill_row >= 0 || R.row_group != 1 ||
+      R.beam_rows || !wo_heads.p ||
       D > 128 || H > 64 || !oproj_fuse_on())
     return false;
   Rows r = R;
@@ -587,9 +634,12 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R, PaPlan* plan) 
     ro.out16 = R.act;
   }
   if (R.row_group >= 4 && beam_steal_on()) ro.beam_ctr = beam_ctr.p;
+  // LLM_FP8 pages: K's scale folded into the score multiplier, V's applied to
+  // the normalised heads by the launch (1 and 1 for fp16 pages)
+  ro.out_scale = v_scale[l];
   RET_IF(pa_decode_internal(&view, R.q, hid, R.o, R.beam_rows, R.ctx, R.n, H, D, cfg.max_seq_len,
-                            cfg.attn_scale, pps, R.attn_ws, R.attn_ws_bytes, st, &ro,
-                            R.row_group, plan));
+                            kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale, pps,
+                            R.attn_ws, R.attn_ws_bytes, st, &ro, R.row_group, plan));
   if (R.wgm_quant && !plan)  // the packed int8 o_proj input + row scales
     LLM_HIP_RET(launch_quantize_rows(R.o, R.n, hid, static_cast<int8_t*>(R.act), R.sa, st, 1));
   return LLM_OK;
@@ -944,10 +994,12 @@ extern "C" int llm_decoder_begin_synthetic(llm_decoder* d, int batch, int contex
   }
   for (int b = 0; b < batch; ++b) RET_IF(kv_cache_reserve(d->kv, b, context_len));
   RET_IF(kv_cache_sync(d->kv, d->stream));
-  // seeded random fp16 K/V over the whole pools (K scaled so q.k ~ O(1))
+  // seeded random K/V over the whole pools (K scaled so q.k ~ O(1)); LLM_FP8
+  // pools hold the same values encoded at scale 1
   const size_t np = (size_t)k->num_pages, pe = k->page_elems, ps = k->page_stride() / k->es;
-  LLM_HIP_RET(launch_fill_random_f16(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
-  LLM_HIP_RET(launch_fill_random_f16(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
+  const auto fill = d->kvt == LLM_FP8 ? launch_fill_random_fp8 : launch_fill_random_f16;
+  LLM_HIP_RET(fill(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
+  LLM_HIP_RET(fill(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
   LLM_HIP_RET(hipStreamSynchronize(d->stream));
   return LLM_OK;
 }
@@ -982,8 +1034,9 @@ extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_wi
   }
   RET_IF(kv_cache_sync(d->kv, d->stream));
   const size_t np = (size_t)k->num_pages, pe = k->page_elems, ps = k->page_stride() / k->es;
-  LLM_HIP_RET(launch_fill_random_f16(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
-  LLM_HIP_RET(launch_fill_random_f16(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
+  const auto fill = d->kvt == LLM_FP8 ? launch_fill_random_fp8 : launch_fill_random_f16;
+  LLM_HIP_RET(fill(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
+  LLM_HIP_RET(fill(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
   LLM_HIP_RET(hipStreamSynchronize(d->stream));
   d->row_group = beam_width;
   d->graph_batch = -1;  // re-capture: the attention launch depends on row_group

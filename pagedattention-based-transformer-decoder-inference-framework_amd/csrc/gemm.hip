@@ -146,10 +146,13 @@ int llm::weight_gemm(const WeightGemm& g, hipStream_t st) {
   if (g.kv) {
     const KvAppendView& kv = *g.kv;
     LLM_REQUIRE(g.N == 3 * kv.H * kv.D && g.K == kv.H * kv.D, "weight_gemm: kv append shape");
+    LLM_REQUIRE(kv.kv_dtype == LLM_F16 || kv.kv_dtype == LLM_FP8,
+                "weight_gemm: kv append into fp16 or fp8 pools");
     a.kv = KvAppend{kv.pos, kv.page_table, kv.rows, static_cast<_Float16*>(kv.k_pool),
                     static_cast<_Float16*>(kv.v_pool), kv.num_beams, kv.max_tiles, kv.page_size,
                     kv.num_pages, kv.H, kv.D,
-                    kv.page_stride > 0 ? kv.page_stride : (size_t)kv.page_size * kv.D};
+                    kv.page_stride > 0 ? kv.page_stride : (size_t)kv.page_size * kv.D,
+                    kv.kv_dtype == LLM_FP8 ? 1 : 0, kv.k_inv_scale, kv.v_inv_scale};
   }
   const hipError_t e = g.dtype == LLM_I8 ? launch_gemm<GemmKind::I8>(a, st)
                                          : launch_gemm<GemmKind::F16>(a, st);

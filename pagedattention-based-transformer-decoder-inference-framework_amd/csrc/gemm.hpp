@@ -18,7 +18,11 @@ struct KvAppendView {
   void* k_pool;
   void* v_pool;
   int num_beams = 0, max_tiles = 0, page_size = 0, num_pages = 0, H = 0, D = 0;
-  size_t page_stride = 0;  // fp16 elements from page p to page p + 1 (0: one page)
+  size_t page_stride = 0;  // elements from page p to page p + 1 (0: one page)
+  // element type of the pools: LLM_F16, or LLM_FP8 (csrc/fp8.hpp) with the
+  // layer's inverse scales (1 / k_scale, 1 / v_scale, computed on the host)
+  int kv_dtype = LLM_F16;
+  float k_inv_scale = 1.f, v_inv_scale = 1.f;
 };
 
 // One decode weight GEMM (decoder-internal form of i8_gemm / f16_gemm):

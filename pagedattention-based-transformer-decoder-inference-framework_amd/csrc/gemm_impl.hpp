@@ -28,6 +28,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "fp8.hpp"
 #include "gemm.hpp"
 #include "ln_wave.hpp"
 
@@ -36,7 +37,9 @@ namespace llm {
 // Optional epilogue target of the fused qkv projection: columns [hid, 2 hid)
 // (K) and [2 hid, 3 hid) (V) of row m are written as fp16 into the page of
 // position pos[m] (KVTileCache::get_write_ptr, kv_cache/kv_tile_cache.hpp:28-34)
-// instead of a separate append launch.
+// instead of a separate append launch.  fp8: the pools hold LLM_FP8 bytes
+// (csrc/fp8.hpp), written as cvt_e4m3(clamp(y * k_inv / v_inv)), one byte
+// store per element; page_stride counts elements of the pools' type.
 struct KvAppend {
   const int32_t* pos;
   const int32_t* page_table;  // [num_beams][H][max_tiles] of this layer (row offset applied)
@@ -45,6 +48,8 @@ struct KvAppend {
   _Float16* v_pool;
   int num_beams, max_tiles, TS, num_pages, H, D;
   size_t page_stride;  // elements from page p to page p + 1
+  int fp8;             // pools of LLM_FP8 bytes (else fp16)
+  float k_inv, v_inv;  // fp8: 1 / k_scale, 1 / v_scale of the layer
 };
 
 struct GemmArgs {
@@ -557,7 +562,11 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
       const int d = i % kv.D;
       const int p = e_pos[e];
       const size_t off = (size_t)e_page[e] * kv.page_stride + (size_t)(p % kv.TS) * kv.D + d;
-      (which ? kv.v_pool : kv.k_pool)[off] = (_Float16)y;
+      if (kv.fp8)
+        reinterpret_cast<uint8_t*>(which ? kv.v_pool : kv.k_pool)[off] =
+            (uint8_t)fp8_e4m3_byte(y, which ? kv.v_inv : kv.k_inv);
+      else
+        (which ? kv.v_pool : kv.k_pool)[off] = (_Float16)y;
     }
   }
   if (stamp && lane == 0) stamp[32 + w] = phase_clock();  // [32, 48): wave end

@@ -59,7 +59,7 @@ int KvCache::init(int L_, int beams_, int H_, int D_, int TS_, int max_tiles_, l
                   int dtype_) {
   L = L_; beams = beams_; H = H_; D = D_; TS = TS_; max_tiles = max_tiles_; num_pages = pages;
   dtype = dtype_;
-  es = dtype == LLM_F32 ? 4 : dtype == LLM_I8 ? 1 : 2;
+  es = dtype == LLM_F32 ? 4 : dtype == LLM_I8 || dtype == LLM_FP8 ? 1 : 2;
   page_elems = (size_t)TS * D;
   // A wave loads K page p and V page p together.  With two separate pools at
   // a large distance the pair often falls into the same HBM channel and the
@@ -286,8 +286,8 @@ extern "C" int kv_cache_create_typed(int num_layers, int num_beams, int num_head
                                      int kv_dtype, kv_cache** out) {
   LLM_REQUIRE(out != nullptr, "kv_cache_create: out is NULL");
   LLM_REQUIRE(kv_dtype == LLM_F16 || kv_dtype == LLM_BF16 || kv_dtype == LLM_F32 ||
-                  kv_dtype == LLM_I8,
-              "kv_cache_create: kv_dtype must be LLM_F16, LLM_BF16, LLM_F32 or LLM_I8");
+                  kv_dtype == LLM_I8 || kv_dtype == LLM_FP8,
+              "kv_cache_create: kv_dtype must be LLM_F16, LLM_BF16, LLM_F32, LLM_I8 or LLM_FP8");
   LLM_REQUIRE(num_layers > 0 && num_beams > 0 && num_heads > 0 && head_dim > 0 && page_size > 0 &&
                   max_tiles > 0 && num_pages > 0,
               "kv_cache_create: all sizes must be positive");

@@ -34,7 +34,8 @@ constexpr uint64_t kMagic = 0x31564B4D49505041ull;    // "APPIMKV1": fp16 pools,
 constexpr uint64_t kMagicV2 = 0x32564B4D49505041ull;  // "APPIMKV2": + kv_dtype word
 constexpr size_t kStagingBytes = 64ull << 20;         // host/device staging per chunk
 
-int elem_bytes(int dtype) { return dtype == LLM_F32 ? 4 : dtype == LLM_I8 ? 1 : 2; }
+// (LLM_FP8 pools are stored as their bytes; no file holds a scale)
+int elem_bytes(int dtype) { return dtype == LLM_F32 ? 4 : dtype == LLM_I8 || dtype == LLM_FP8 ? 1 : 2; }
 
 long long file_size(std::ifstream& f) {
   f.seekg(0, std::ios::end);
@@ -153,7 +154,7 @@ int parse_snapshot(std::ifstream& f, const char* path, Snapshot& s) {
   const int64_t L = s.geo[0], beams = s.geo[1], H = s.geo[2], D = s.geo[3], TS = s.geo[4],
                 mt = s.geo[5], np = s.geo[6], dt = s.geo[7];
   if (L <= 0 || beams <= 0 || H <= 0 || D <= 0 || TS <= 0 || mt <= 0 || np <= 0 ||
-      np >= (1LL << 31) || D > (1 << 16) || TS > (1 << 16) || TS * D > (1 << 24) || (dt != LLM_F16 && dt != LLM_BF16 && dt != LLM_F32 && dt != LLM_I8))
+      np >= (1LL << 31) || D > (1 << 16) || TS > (1 << 16) || TS * D > (1 << 24) || (dt != LLM_F16 && dt != LLM_BF16 && dt != LLM_F32 && dt != LLM_I8 && dt != LLM_FP8))
     return fail(LLM_ERR_IO, "kv_cache snapshot " + p + ": bad geometry");
   // entries * 4 must fit in the file before anything is allocated
   const long long room = (size - off) / 4;

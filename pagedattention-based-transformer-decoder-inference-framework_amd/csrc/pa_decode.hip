@@ -25,6 +25,7 @@ struct PaMergeRowArgs {
   int B, H, D, T, TS, pps, nsplit, max_tiles;
   int pack;  // q / out16 in packed-A order (common.hpp a_frag_off_*)
   int ctx_p0;  // >= 0 and context_lens NULL: row b's context is ctx_p0 + b + 1 (prefill)
+  float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
 };
 
 // One head's split merge (flash-decoding LSE combine) by one wave, DPL =
@@ -114,6 +115,7 @@ struct PaMergeArgs {
   float* out;
   const int32_t* context_lens;
   int B, H, D, T, TS, pps, nsplit, max_tiles;
+  float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
 };
 
 template <int DPL>
@@ -129,9 +131,9 @@ __global__ __launch_bounds__(256) void pa_merge_kernel(PaMergeArgs a) {
   // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
   const int ns = a.pps < 0 ? a.nsplit : min(a.nsplit, (ntiles + pps - 1) / pps);
   float acc[DPL];
-  const float inv = merge_head<DPL, 16>(a.part_ml + (size_t)bh * a.nsplit * 2,
-                                        a.part_acc + (size_t)bh * a.nsplit * a.D, a.nsplit, ns,
-                                        a.D, acc);
+  const float inv = a.out_scale * merge_head<DPL, 16>(a.part_ml + (size_t)bh * a.nsplit * 2,
+                                                      a.part_acc + (size_t)bh * a.nsplit * a.D,
+                                                      a.nsplit, ns, a.D, acc);
   float* o = a.out + (size_t)bh * a.D;
 #pragma unroll
   for (int j = 0; j < DPL; ++j) {
@@ -161,9 +163,9 @@ __global__ __launch_bounds__(1024) void pa_merge_row_kernel(PaMergeRowArgs a) {
   for (int h = w; h < a.H; h += nw) {
     const size_t bh = (size_t)b * a.H + h;
     float acc[DPL];
-    const float inv = merge_head<DPL, kMergeBatch>(a.part_ml + bh * a.nsplit * 2,
-                                                   a.part_acc + bh * a.nsplit * a.D, a.nsplit, ns,
-                                                   a.D, acc);
+    const float inv = a.out_scale * merge_head<DPL, kMergeBatch>(a.part_ml + bh * a.nsplit * 2,
+                                                                 a.part_acc + bh * a.nsplit * a.D,
+                                                                 a.nsplit, ns, a.D, acc);
     float* dst = row + h * a.D;
 #pragma unroll
     for (int j = 0; j < DPL; ++j) {
@@ -262,6 +264,13 @@ namespace {
 // 82.3 at 12 splits, against 67.6 us; MFMA 69.8 vs 60.8 us; steal 76-92 vs
 // 65.3 us).
 
+// LLM_FP8 pools merge in the workgroup for pages up to 2 KiB (64 or 128 dims x
+// 16 tokens, 64 x 32: C3's and C5's shape among them).  Larger pages hold more
+// decoded elements live per stage than the form's 512-thread bound (256 VGPRs)
+// leaves room for -- 128 x 32 and 256 x 16 spill 76-80 bytes per lane, 256 x 32
+// 224 -- so they keep split + merge.
+constexpr bool fp8_wgm_shape_ok(int D, int TS) { return D * TS <= 2048; }
+
 template <int D, int TS, int KVT>
 hipError_t launch_split(const PaSplitArgs& a, bool direct, hipStream_t st, bool* beam) {
   const int waves = ((a.B + a.group - 1) / a.group) * a.group * a.H * a.nsplit;
@@ -269,6 +278,16 @@ hipError_t launch_split(const PaSplitArgs& a, bool direct, hipStream_t st, bool*
   if constexpr (KVT != LLM_F16) {
     // other KV element types: the standard schedule (no beam-prefetch form)
     constexpr int ST = split_stages<D, TS, KVT>();
+    if constexpr (KVT == LLM_FP8 && fp8_wgm_shape_ok(D, TS)) {
+      // the decoder's own forms: the workgroup merge as well (no fused o_proj:
+      // pa_decode_internal refuses o_acc with these pools)
+      if (a.wgm) {
+        hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST, 0, false, false,
+                                            LLM_FP8, true, true>),
+                           dim3(a.B * a.H), dim3(64 * a.nsplit), 0, st, a);
+        return hipGetLastError();
+      }
+    }
     if (direct)
       hipLaunchKernelGGL((pa_split_kernel<D, TS, true, 16384, kKvLoadAux, ST, 0, false, false, KVT>),
                          grid, block, 0, st, a);
@@ -337,6 +356,7 @@ hipError_t dispatch_kvt(const PaSplitArgs& a, int kvt, int TS, bool direct, hipS
     case LLM_BF16: return dispatch_ts<D, LLM_BF16>(a, TS, direct, st, beam);
     case LLM_F32: return dispatch_ts<D, LLM_F32>(a, TS, direct, st, beam);
     case LLM_I8: return dispatch_ts<D, LLM_I8>(a, TS, direct, st, beam);
+    case LLM_FP8: return dispatch_ts<D, LLM_FP8>(a, TS, direct, st, beam);
     default: return hipErrorInvalidValue;
   }
 }
@@ -345,7 +365,7 @@ int kv_dtype_bytes(int kvt) {
   switch (kvt) {
     case LLM_F16: case LLM_BF16: return 2;
     case LLM_F32: return 4;
-    case LLM_I8: return 1;
+    case LLM_I8: case LLM_FP8: return 1;
     default: return 0;
   }
 }
@@ -425,6 +445,7 @@ long long resident_for_kvt(int TS, int kvt) {
     case LLM_BF16: return by_ts(std::integral_constant<int, LLM_BF16>{});
     case LLM_F32: return by_ts(std::integral_constant<int, LLM_F32>{});
     case LLM_I8: return by_ts(std::integral_constant<int, LLM_I8>{});
+    case LLM_FP8: return by_ts(std::integral_constant<int, LLM_FP8>{});
     default: return by_ts(std::integral_constant<int, LLM_F16>{});
   }
 }
@@ -470,8 +491,10 @@ extern "C" size_t pa_decode_workspace_bytes(int B, int H, int D, int max_tiles,
 
 int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                                   const int32_t* context_lens, int B, int H, int D, int T, int TS,
-                                  int pps, int nsplit, int max_tiles, hipStream_t st) {
-  PaMergeArgs mg{part_acc, part_ml, out, context_lens, B, H, D, T, TS, pps, nsplit, max_tiles};
+                                  int pps, int nsplit, int max_tiles, hipStream_t st,
+                                  float out_scale) {
+  PaMergeArgs mg{part_acc, part_ml, out, context_lens, B, H, D, T, TS, pps, nsplit, max_tiles,
+                 out_scale};
   const dim3 grid((B * H + 3) / 4);
   if (D <= 64)
     hipLaunchKernelGGL(pa_merge_kernel<1>, grid, dim3(256), 0, st, mg);
@@ -486,11 +509,11 @@ int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, f
 int llm::pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                                 const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                                 int B, int H, int D, int T, int TS, int pps, int nsplit,
-                                int max_tiles, hipStream_t st) {
+                                int max_tiles, hipStream_t st, float out_scale) {
   PaMergeRowArgs mg{part_acc, part_ml, out, rows ? rows->q : nullptr,
                     rows ? rows->inv_scale : nullptr,
                     rows ? static_cast<_Float16*>(rows->out16) : nullptr, context_lens, B, H, D, T,
-                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0};
+                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0, out_scale};
   const int threads = 64 * std::min(16, H);  // one wave per head (heads > 16 loop)
   const size_t lds = (size_t)H * D * sizeof(float);
   if (D <= 64)
@@ -572,7 +595,7 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
   LLM_REQUIRE(!rows || !rows->pack || (H * D) % 64 == 0, "pa_decode: packed row outputs need H*D % 64 == 0");
   LLM_REQUIRE(kv->k_pool && kv->v_pool && kv->page_table, "pa_decode: kv pointers NULL");
   LLM_REQUIRE(kv_dtype_bytes(kv->kv_dtype) > 0,
-              "pa_decode: kv_dtype must be LLM_F16, LLM_BF16, LLM_F32 or LLM_I8");
+              "pa_decode: kv_dtype must be LLM_F16, LLM_BF16, LLM_F32, LLM_I8 or LLM_FP8");
   LLM_REQUIRE(kv->num_heads == H, "pa_decode: H != kv->num_heads");
   LLM_REQUIRE(kv->head_dim == D, "pa_decode: D != kv->head_dim");
   LLM_REQUIRE(kv->num_pages > 0 && kv->num_beams > 0 && kv->max_tiles > 0,
@@ -614,12 +637,19 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
   // profiles/r05/attention_b8_split_sweep.txt): 85.6 -> 84.3 us, the
   // loads-only form 83.7 / 83.4 us at either count.
   const bool half_round = f32_rows && row_group == 1 && pps_fixed <= 0 &&
-                          kv->kv_dtype == LLM_F16 && nsplit > kWgmMaxSplits &&
+                          (kv->kv_dtype == LLM_F16 || kv->kv_dtype == LLM_FP8) &&
+                          nsplit > kWgmMaxSplits &&
                           (long long)B * H * nsplit == resident_launch &&
                           (ntiles_max + nsplit - 1) / nsplit <= 2 * kShortPps;
   if (half_round) nsplit = (nsplit + 1) / 2;
+  // fp16 pools, and fp8 pools for the fp32-row merge (the INT8 decoder's): the
+  // fused o_proj and the fp16 row output of the workgroup merge are fp16-KV
+  // forms, so an FP16-weights decoder on fp8 pages runs split + merge-row
+  const bool wgm_kvt = kv->kv_dtype == LLM_F16 ||
+                       (kv->kv_dtype == LLM_FP8 && !oproj && !(rows && rows->out16) &&
+                        fp8_wgm_shape_ok(D, TS));
   const bool wgm_ok = ((row_out && rows->out16 && !rows->q) || oproj || f32_rows) && row_group == 1 &&
-                      kv->kv_dtype == LLM_F16 && tn.wg_merge && !half_round;
+                      wgm_kvt && tn.wg_merge && !half_round;
   if (wgm_ok && pps_fixed <= 0 && !f32_rows) {
     const int nw = choose_nsplit(B, H, ntiles_max, 0, resident_launch, kWgmShortPps);
     if (nw >= 2 && nw <= kWgmMaxSplits) nsplit = nw;
@@ -685,7 +715,8 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
                                        : tune_steal_counters(2 * (size_t)((B + 3) / 4) * H);
   LLM_REQUIRE(!direct || out != nullptr, "pa_decode: single-split launch needs the fp32 out");
   if (oproj && (direct || row_group != 1 || nsplit > kWgmMaxSplits || !wgm_ok))
-    return fail(LLM_ERR_UNSUPPORTED, "pa_decode: the fused o_proj needs the workgroup-merge form");
+    return fail(LLM_ERR_UNSUPPORTED,
+                "pa_decode: the fused o_proj needs the workgroup-merge form over fp16 pools");
 
   PaSplitArgs a{};
   a.k_pool = static_cast<const uint8_t*>(kv->k_pool);
@@ -707,6 +738,8 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
   a.nsplit = nsplit;
   a.group = std::max(1, std::min(row_group, 4));
   a.qscale = sm_scale * kLog2e;
+  const float out_scale = rows && kv->kv_dtype == LLM_FP8 ? rows->out_scale : 1.f;
+  a.out_scale = out_scale;
   const bool wgm = wgm_ok && !direct && a.group == 1 && nsplit <= kWgmMaxSplits;
   if (!direct && !wgm) {  // (the workgroup merge keeps its splits' states in LDS)
     const size_t need = (size_t)B * H * nsplit * (size_t)(D + 2) * sizeof(float);
@@ -749,10 +782,11 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
   if (row_out && !direct)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, rows->keep_out ? out : nullptr, rows,
                                   context_lens, -1, B, H, D, T, TS, beam ? -1 : pps_fixed, nsplit,
-                                  kv->max_tiles, st);
+                                  kv->max_tiles, st, out_scale);
   if (!direct) {
     const int r = pa_merge_splits_internal(a.part_acc, a.part_ml, out, context_lens, B, H, D, T,
-                                           TS, beam ? -1 : pps_fixed, nsplit, kv->max_tiles, st);
+                                           TS, beam ? -1 : pps_fixed, nsplit, kv->max_tiles, st,
+                                           out_scale);
     if (r != LLM_OK) return r;
   }
   if (row_out) {  // single split: out is final; convert it in a row pass

@@ -41,6 +41,10 @@ struct PaRowOutputs {
   // the launch assigns tiles dynamically (csrc/tune/pa_beam_steal.hpp,
   // LLM_PA_FORM_STEAL), without them it runs the static BEAM form
   unsigned* beam_ctr = nullptr;
+  // LLM_FP8 pools: the layer's V scale, multiplied into the normalised output
+  // once per (row, head) by every launch form, before any of the conversions
+  // above rounds it (K's scale is the caller's to fold into sm_scale)
+  float out_scale = 1.f;
 };
 
 // The launch a call takes (pa_decode_plan): splits per (row, head) and
@@ -72,14 +76,16 @@ bool beam_steal_on();
 // (out fp32 [B][H*D] and/or the rows->q / out16 o_proj inputs); row b's
 // context is context_lens[b], or ctx_p0 + b + 1 when context_lens is NULL and
 // ctx_p0 >= 0, or T.  Split s of a row covers tiles [s*pps, (s+1)*pps).
+// out_scale multiplies every merged head (LLM_FP8 pools: the V scale).
 int pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                            const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                            int B, int H, int D, int T, int TS, int pps, int nsplit, int max_tiles,
-                           hipStream_t st);
+                           hipStream_t st, float out_scale = 1.f);
 
 int pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                              const int32_t* context_lens, int B, int H, int D, int T, int TS,
-                             int pps, int nsplit, int max_tiles, hipStream_t st);
+                             int pps, int nsplit, int max_tiles, hipStream_t st,
+                             float out_scale = 1.f);
 
 // Causal MFMA attention of a prompt chunk (csrc/pa_prefill.hip, C entry
 // pa_prefill): out rows i < m = attention of query i (position p0 + i) over
@@ -96,7 +102,10 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
 
 // Bytes per element of a KV pool type (0: unknown type).
 inline int kv_elem_size(int kvt) {
-  return kvt == LLM_F16 || kvt == LLM_BF16 ? 2 : kvt == LLM_F32 ? 4 : kvt == LLM_I8 ? 1 : 0;
+  return kvt == LLM_F16 || kvt == LLM_BF16 ? 2
+         : kvt == LLM_F32                  ? 4
+         : kvt == LLM_I8 || kvt == LLM_FP8 ? 1
+                                           : 0;
 }
 
 // Bytes from page p to page p + 1 of a view's pools (page_stride 0 = dense).

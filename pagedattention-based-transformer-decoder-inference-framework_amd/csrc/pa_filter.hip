@@ -64,6 +64,8 @@ __device__ __forceinline__ float kv_elem(const uint8_t* pool, size_t i) {
     return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(pool)[i] << 16);
   } else if constexpr (KVT == LLM_F32) {
     return reinterpret_cast<const float*>(pool)[i];
+  } else if constexpr (KVT == LLM_FP8) {  // OCP e4m3fn, read as a plain number (scale 1)
+    return __builtin_amdgcn_cvt_f32_fp8((int)pool[i], 0);
   } else {
     return (float)reinterpret_cast<const int8_t*>(pool)[i];
   }
@@ -323,6 +325,7 @@ extern "C" int pa_decode_ex(const pa_kv_view* kv, const float* q, float* out,
     case LLM_BF16: LLM_FILTER_LAUNCH(LLM_BF16); break;
     case LLM_F32: LLM_FILTER_LAUNCH(LLM_F32); break;
     case LLM_I8: LLM_FILTER_LAUNCH(LLM_I8); break;
+    case LLM_FP8: LLM_FILTER_LAUNCH(LLM_FP8); break;
     default: return fail(LLM_ERR_INVALID, "pa_decode_ex: kv_dtype");
   }
 #undef LLM_FILTER_LAUNCH

@@ -101,7 +101,12 @@ struct PaSplitArgs {
   // workgroups (blockIdx b, b + 256, b + 512, b + 768 at C4) are then 4 split
   // pairs of 4 (group, head)s rather than 4 sequence pairs, and the splits of
   // one (group, head) share an XCD (blockIdx mod 8) and its L2.
-  int smaj;  // (last: the earlier fields keep their kernel-argument offsets)
+  int smaj;  // (the earlier fields keep their kernel-argument offsets)
+  // LLM_FP8 pools: the V scale of the layer, multiplied into the normalised
+  // output once per (row, head) by whichever kernel writes it (the direct
+  // form and the workgroup merge here, the merge kernels otherwise); K's scale
+  // arrives folded into qscale.  Other element types never read it.
+  float out_scale;
 };
 
 constexpr int kWgmMaxSplits = 8;  // one merge batch (pa_merge_row_kernel's kMergeBatch)
@@ -125,9 +130,12 @@ constexpr int pages_per_stage() {
 // KV element types of the pools (AttentionCUDA::forward's T in {__half, bf16,
 // int8_t, float}, attention/attention_cuda.cu:58-94).  int8 is the raw value
 // (KVTileCache<int8_t> stores and the kernel reads it as a number, no scale).
+// LLM_FP8 is OCP e4m3fn (csrc/fp8.hpp): the kernel reads the decoded number;
+// a layer's scales reach it through qscale (K) and out_scale (V), so they cost
+// nothing per element.
 template <int KVT>
 constexpr int kv_elem_bytes() {
-  return KVT == LLM_F32 ? 4 : KVT == LLM_I8 ? 1 : 2;
+  return KVT == LLM_F32 ? 4 : KVT == LLM_I8 || KVT == LLM_FP8 ? 1 : 2;
 }
 
 // Element e of a lane's 16-byte KV piece as fp32.
@@ -140,6 +148,14 @@ __device__ __forceinline__ float kv_at(const u32x4& r, int e) {
     return __uint_as_float((e & 1) ? (w & 0xFFFF0000u) : (w << 16));
   } else if constexpr (KVT == LLM_F32) {
     return __uint_as_float(r[e]);
+  } else if constexpr (KVT == LLM_FP8) {
+    // v_cvt_pk_f32_fp8 converts half a word (two elements) per instruction;
+    // the callers' unrolled loops over e share each conversion between its
+    // two elements, so a 16-element piece costs 8 converts
+    // (the half select is an immediate of the builtin: one call per half)
+    const int w = (int)r[e >> 2];
+    return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1]
+                   : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
   } else {
     return (float)(((int32_t)r[e >> 2] << (24 - 8 * (e & 3))) >> 24);
   }
@@ -748,7 +764,8 @@ void pa_split_kernel(PaSplitArgs a) {
             const float ws = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w0), s2));
             L += ls * ws;
           }
-        const float inv = 1.0f / (L + 1e-6f);
+        float inv = 1.0f / (L + 1e-6f);
+        if constexpr (KVT == LLM_FP8) inv *= a.out_scale;  // V's scale, folded as the merge kernels fold it
         float am[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; ++e) am[e] = 0.f;
@@ -772,7 +789,7 @@ void pa_split_kernel(PaSplitArgs a) {
         }
         if (a.out16) {
           static_assert(KVT != LLM_F16 || EPL == 8, "fp16 lanes hold 8 dims: one 16-byte store");
-          if constexpr (EPL == 8) {
+          if constexpr (EPL == 8) {  // (fp16 pools only: pa_decode_internal's wgm_ok)
             f16x8 pk;
 #pragma unroll
             for (int e = 0; e < 8; ++e) pk[e] = (_Float16)o[e];
@@ -839,7 +856,8 @@ void pa_split_kernel(PaSplitArgs a) {
 
   if (lane < LPT) {
     if constexpr (DIRECT) {
-      const float inv = 1.0f / (l + 1e-6f);
+      float inv = 1.0f / (l + 1e-6f);
+      if constexpr (KVT == LLM_FP8) inv *= a.out_scale;  // V's scale (1 through the public entries)
       float* o = a.out + (size_t)bh * D + c * EPL;
 #pragma unroll
       for (int e = 0; e < EPL; e += 4)

@@ -2,6 +2,7 @@
 // per-row int8 quantisation, embedding gather, KV append into pages, argmax.
 // All are one workgroup per row, vectorised 16 B per lane where the row allows.
 #include "common.hpp"
+#include "fp8.hpp"
 #include "gemm.hpp"
 #include "ln_wave.hpp"
 #include "row_ops.hpp"
@@ -350,8 +351,10 @@ __global__ void scatter_i32_kernel(int32_t* __restrict__ dst, const int64_t* __r
 // Element i of the n = pages * page_elems lands at p[(i / page_elems) *
 // page_stride + i % page_elems] (page_stride in elements: a pool whose pages
 // interleave with another pool's).
-__global__ void fill_random_f16_kernel(_Float16* __restrict__ p, size_t n, size_t page_elems,
-                                       size_t page_stride, uint64_t seed, float scale) {
+// T = _Float16, or uint8_t: LLM_FP8 bytes (csrc/fp8.hpp) of the same seeded values at scale 1
+template <typename T>
+__global__ void fill_random_kernel(T* __restrict__ p, size_t n, size_t page_elems,
+                                   size_t page_stride, uint64_t seed, float scale) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
@@ -362,7 +365,12 @@ __global__ void fill_random_f16_kernel(_Float16* __restrict__ p, size_t n, size_
     float u = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) u += (float)((z >> (16 * k)) & 0xFFFF) * (1.0f / 65536.0f);
-    p[(i / page_elems) * page_stride + i % page_elems] = (_Float16)((u - 2.0f) * 1.7320508f * scale);
+    const float v = (u - 2.0f) * 1.7320508f * scale;
+    T* dst = p + (i / page_elems) * page_stride + i % page_elems;
+    if constexpr (sizeof(T) == 1)
+      *dst = (T)fp8_e4m3_byte(v, 1.0f);
+    else
+      *dst = (T)v;
   }
 }
 
@@ -462,8 +470,18 @@ hipError_t launch_fill_random_f16(void* p, size_t pages, size_t page_elems, size
   const size_t n = pages * page_elems;
   if (n == 0) return hipSuccess;
   const size_t blocks = std::min<size_t>((n + 255) / 256, 65536);
-  hipLaunchKernelGGL(fill_random_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
+  hipLaunchKernelGGL(fill_random_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st,
                      static_cast<_Float16*>(p), n, page_elems, page_stride, seed, scale);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_random_fp8(void* p, size_t pages, size_t page_elems, size_t page_stride,
+                                  uint64_t seed, float scale, hipStream_t st) {
+  const size_t n = pages * page_elems;
+  if (n == 0) return hipSuccess;
+  const size_t blocks = std::min<size_t>((n + 255) / 256, 65536);
+  hipLaunchKernelGGL(fill_random_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, st,
+                     static_cast<uint8_t*>(p), n, page_elems, page_stride, seed, scale);
   return hipGetLastError();
 }
 

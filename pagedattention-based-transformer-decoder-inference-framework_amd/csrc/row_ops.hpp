@@ -47,5 +47,9 @@ hipError_t launch_sample(const float* logits, int rows, int row0, int V, float t
 // elements, page p at p + p * page_stride elements.
 hipError_t launch_fill_random_f16(void* p, size_t pages, size_t page_elems, size_t page_stride,
                                   uint64_t seed, float scale, hipStream_t st);
+// The same seeded values as LLM_FP8 bytes (csrc/fp8.hpp) at scale 1;
+// page_stride in bytes.
+hipError_t launch_fill_random_fp8(void* p, size_t pages, size_t page_elems, size_t page_stride,
+                                  uint64_t seed, float scale, hipStream_t st);
 
 }  // namespace llm

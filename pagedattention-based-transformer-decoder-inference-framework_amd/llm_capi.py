@@ -21,7 +21,7 @@ TUNE_LIB_PATH = HERE / "libllm_decoder_hip_tune.so"  # `make tune`: A/B hooks, n
 
 (LLM_OK, LLM_ERR_INVALID, LLM_ERR_UNSUPPORTED, LLM_ERR_HIP, LLM_ERR_OOM, LLM_ERR_IO,
  LLM_ERR_RANGE) = range(7)
-LLM_F16, LLM_I8, LLM_F32, LLM_BF16 = 0, 1, 2, 3
+LLM_F16, LLM_I8, LLM_F32, LLM_BF16, LLM_FP8 = 0, 1, 2, 3, 4
 LLM_ACT_NONE, LLM_ACT_RELU, LLM_ACT_GELU = 0, 1, 2
 LLM_EVICT_NONE, LLM_EVICT_LRU = 0, 1
 
@@ -55,6 +55,13 @@ class LlmError(RuntimeError):
 _SIGS = {
     "llm_last_error": (ctypes.c_char_p, []),
     "llm_abi_version": (c_int, []),
+    "llm_fp8_e4m3_encode": (c_int, [c_void_p, c_size_t, c_float, c_void_p]),
+    "llm_fp8_e4m3_decode": (c_int, [c_void_p, c_size_t, c_float, c_void_p]),
+    "llm_decoder_create_kv": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
+    "llm_decoder_set_kv_scales": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "llm_decoder_kv_dtype": (c_int, [c_void_p]),
+    "llm_decoder_destroy": (None, [c_void_p]),
+    "llm_decoder_begin_synthetic": (c_int, [c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "pa_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "pa_decode_pages_per_split": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pa_decode_plan": (c_int, [ctypes.POINTER(PaKvView), c_int, c_int, c_int, c_int, c_int, c_int,
@@ -196,18 +203,36 @@ def ptr(t) -> ctypes.c_void_p:
 
 
 def kv_dtype_of(t) -> int:
-    """llm_dtype of a torch KV pool tensor (fp16, bf16, fp32 or int8)."""
+    """llm_dtype of a torch KV pool tensor (fp16, bf16, fp32, int8 or float8_e4m3fn)."""
     import torch
     m = {torch.float16: LLM_F16, torch.bfloat16: LLM_BF16, torch.float32: LLM_F32,
-         torch.int8: LLM_I8}
+         torch.int8: LLM_I8, torch.float8_e4m3fn: LLM_FP8}
     if t.dtype not in m:
-        raise TypeError(f"KV pool dtype {t.dtype} is not one of fp16/bf16/fp32/int8")
+        raise TypeError(f"KV pool dtype {t.dtype} is not one of fp16/bf16/fp32/int8/float8_e4m3fn")
     return m[t.dtype]
 
 
+def fp8_encode(x, scale: float = 1.0):
+    """llm_fp8_e4m3_encode of a float32 numpy array: uint8 array of the same shape."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.shape, dtype=np.uint8)
+    check(load().llm_fp8_e4m3_encode(x.ctypes.data, x.size, scale, out.ctypes.data))
+    return out
+
+
+def fp8_decode(b, scale: float = 1.0):
+    """llm_fp8_e4m3_decode of a uint8 numpy array: float32 array of the same shape."""
+    import numpy as np
+    b = np.ascontiguousarray(b, dtype=np.uint8)
+    out = np.empty(b.shape, dtype=np.float32)
+    check(load().llm_fp8_e4m3_decode(b.ctypes.data, b.size, scale, out.ctypes.data))
+    return out
+
+
 def kv_view(k_pool, v_pool, page_table, *, num_beams=None) -> PaKvView:
-    """View over torch device tensors k/v [num_pages][ts][D] (fp16, bf16, fp32
-    or int8, both the same) and page table int32 [num_beams][H][max_tiles].
+    """View over torch device tensors k/v [num_pages][ts][D] (fp16, bf16, fp32,
+    int8 or float8_e4m3fn, both the same) and page table int32 [num_beams][H][max_tiles].
     Pages may be strided (e.g. k = kv[:, 0], v = kv[:, 1] of one
     [num_pages][2][ts][D] tensor: K and V pages interleaved) as long as each
     page is contiguous; the view's page_stride is then the page-to-page step."""
