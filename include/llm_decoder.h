@@ -163,8 +163,11 @@ int pa_decode_grouped(const pa_kv_view* kv, const float* q, float* out, const in
  * context_lens[i] = p0 + i + 1 (within 1e-3 relative), but each K/V page is
  * read once per 32 queries instead of once per query (MFMA tiles).
  * q, out: fp32 [m][H][D] with row strides q_stride / out_stride floats
- * (<= 0: H*D), 16-byte aligned.  fp16 pools, head_dim 64 or 128, page_size
- * 16 or 32 (else LLM_ERR_UNSUPPORTED; pa_decode covers every shape).
+ * (<= 0: H*D), 16-byte aligned.  fp16 or LLM_FP8 pools, head_dim 64 or 128,
+ * page_size 16 or 32 (else LLM_ERR_UNSUPPORTED; pa_decode covers every shape).
+ * LLM_FP8 pools are read as plain numbers (scale 1, as pa_decode: fold a K
+ * scale into sm_scale); their bytes are decoded to fp16 exactly, so the result
+ * is bit-equal to the same call on fp16 pools holding the decoded values.
  * With workspace_bytes >= pa_prefill_workspace_bytes(kv, p0, m) (and
  * out_stride H*D) the key range is split over more workgroups and merged as
  * pa_decode's splits; with less (or NULL) it runs in one pass. */
@@ -401,8 +404,8 @@ int llm_decoder_create(const llm_decoder_config* cfg, llm_decoder** out);
  * attention reads them; the default num_pages is the same number of pages, so
  * the pool is half the bytes).  Any other element type is LLM_ERR_UNSUPPORTED,
  * an unknown one LLM_ERR_INVALID, decided before any device allocation.
- * Prompt chunks of an LLM_FP8 decoder run their attention through the decode
- * kernel (pa_prefill reads fp16 pools only). */
+ * Prompt chunks of an LLM_FP8 decoder run their attention on the MFMA prefill
+ * kernel for the shapes an fp16-KV decoder does (llm_decoder_prefill_kernel). */
 int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype, llm_decoder** out);
 /* Per-layer scales of an LLM_FP8 decoder: host arrays [num_layers], NULL = all
  * 1.0 (the default), every value finite and > 0.  Allowed only while no rows
@@ -414,6 +417,13 @@ int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype, llm_decod
 int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale, const float* v_scale);
 /* LLM_F16 or LLM_FP8. */
 int llm_decoder_kv_dtype(const llm_decoder* d);
+/* The attention kernel prompt chunks (llm_decoder_prefill, the prompts of
+ * llm_decoder_generate) of this decoder's pools take: LLM_PREFILL_MFMA
+ * (pa_prefill: fp16 or LLM_FP8 pools, head_dim 64 or 128, page_size 16 or 32)
+ * or LLM_PREFILL_DECODE (every other shape: the decode kernel, one row per
+ * prompt token).  -1 for NULL. */
+enum { LLM_PREFILL_DECODE = 0, LLM_PREFILL_MFMA = 1 };
+int llm_decoder_prefill_kernel(const llm_decoder* d);
 void llm_decoder_destroy(llm_decoder* d);
 
 /* Host weights (row-major reference layouts), uploaded and packed on device.

@@ -13,7 +13,8 @@
 //       web/app.py:23, cli/chat_cli.py:24 — fills output_ids in place)
 // and both return / fill prompt + generated ids (cuda_decoder.cu:49,59).
 // Both decoders take a keyword kv_dtype ("float16" by default; "fp8" /
-// "float8_e4m3fn": LLM_FP8 KV pages with per-layer scales, set_kv_scales).
+// "float8_e4m3fn": LLM_FP8 KV pages with per-layer scales, set_kv_scales) and
+// have a read-only prefill_kernel ("mfma" / "decode": llm_decoder_prefill_kernel).
 // Additions: generate_batch, set_weights (host numpy arrays), low-level
 // begin_synthetic / step for the bench, PageTable / KVTileCache classes with
 // the kv_cache/ API names (page_table.hpp:5-37, kv_tile_cache.hpp:9-41) and
@@ -266,6 +267,10 @@ class Decoder {
   std::string kv_dtype() const {
     return llm_decoder_kv_dtype(d_) == LLM_FP8 ? "float8_e4m3fn" : "float16";
   }
+  // llm_decoder_prefill_kernel: the attention kernel prompt chunks take
+  std::string prefill_kernel() const {
+    return llm_decoder_prefill_kernel(d_) == LLM_PREFILL_MFMA ? "mfma" : "decode";
+  }
   const llm_decoder_config& config() const { return cfg_; }
 
  private:
@@ -487,6 +492,7 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("set_kv_scales", &Decoder::set_kv_scales, py::arg("k_scale") = py::none(),
              py::arg("v_scale") = py::none())
         .def_property_readonly("kv_dtype", &Decoder::kv_dtype)
+        .def_property_readonly("prefill_kernel", &Decoder::prefill_kernel)
         .def_property_readonly("kv_handle", &Decoder::kv_handle);
   };
   py::class_<Decoder>(m, "_Decoder");

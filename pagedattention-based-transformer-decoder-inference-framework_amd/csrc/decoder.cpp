@@ -275,6 +275,13 @@ extern "C" int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype
 
 extern "C" int llm_decoder_kv_dtype(const llm_decoder* d) { return d ? d->kvt : -1; }
 
+extern "C" int llm_decoder_prefill_kernel(const llm_decoder* d) {
+  if (!d) return -1;
+  pa_kv_view view;  // layer_attn's own test, on the same view
+  if (kv_cache_view(d->kv, 0, &view) != LLM_OK) return -1;
+  return pa_prefill_supported(&view) ? LLM_PREFILL_MFMA : LLM_PREFILL_DECODE;
+}
+
 extern "C" int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale,
                                          const float* v_scale) {
   LLM_REQUIRE(d, "llm_decoder_set_kv_scales: NULL");
@@ -610,8 +617,11 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R, PaPlan* plan) 
     } else {
       ro.out16 = R.act;
     }
+    // LLM_FP8 pages: the scales enter as in the decode launch below
+    ro.out_scale = v_scale[l];
     return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n,
-                               cfg.attn_scale, R.attn_ws, R.attn_ws_bytes, st, &ro);
+                               kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale,
+                               R.attn_ws, R.attn_ws_bytes, st, &ro);
   }
   // the split merge also produces the o_proj input (packed int8 + scale, or fp16);
   // the fp32 rows are only needed by a single-split (direct) launch

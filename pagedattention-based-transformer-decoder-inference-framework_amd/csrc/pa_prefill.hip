@@ -30,9 +30,17 @@
 // of every p < 0.25 was lost (1e-5 .. 5e-5 output error, measured).  Scaled,
 // products of fp16 pairs are exact in the fp32 accumulator and the output
 // error is at the decode kernel's level (scripts/diag_prefill.py).
+//
+// LLM_FP8 pools (KVT = LLM_FP8): a lane's chunk of a key row arrives as 8 e4m3
+// bytes (half the global traffic and staging registers of fp16) and is decoded
+// to fp16 on its way into LDS (fp8x4_to_f16 below).  Every e4m3 value is an
+// fp16 normal (2^-9 .. 448), so the decode is exact, the LDS layout and all of
+// the math are the fp16 instantiation's, and the output is bit-equal to the
+// fp16 kernel's on pools holding the decoded values.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "pa_decode.hpp"
@@ -59,11 +67,15 @@ struct PaPrefillArgs {
   int nsplit, pps;
   float* part_acc;
   float* part_ml;
+  // multiplies the normalised head of the one-pass form (LLM_FP8: the V scale;
+  // the split form hands it to the merge)
+  float out_scale;
 };
 
 constexpr int kKeyBlock = 32;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 constexpr float kPScale = 16384.f;  // P enters the PV MFMA as p * 2^14 (hi + lo)
 
 __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
@@ -71,13 +83,25 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
   lo = (_Float16)(x - (float)hi);
 }
 
-template <int D, int TS, int NW>
+// Four e4m3 bytes of `w` as four fp16 values (two dwords, element order kept).
+// v_cvt_scalef32_pk_f16_fp8 with scale 1 (2^0) converts two bytes per VALU op
+// straight to packed fp16; NaN codes (0x7F / 0xFF) come out as fp16 NaN.
+__device__ __forceinline__ u32x2 fp8x4_to_f16(uint32_t w) {
+  return u32x2{
+      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)),
+      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))};
+}
+
+template <int KVT, int D, int TS, int NW>
 __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
+  static_assert(KVT == LLM_F16 || KVT == LLM_FP8, "KV element type");
+  constexpr bool FP8 = KVT == LLM_FP8;
+  constexpr int ES = FP8 ? 1 : 2;  // bytes per pool element
   constexpr int KB = kKeyBlock;
   constexpr int KSTR = D + 8;   // K row stride (halves): conflict-free 16-B row reads
   constexpr int VSTR = D + 16;  // V row stride (halves): 8·odd dwords, so the
                                 // 64 lanes of a transposed read hit 64 banks
-  constexpr int CPR = D / 8;    // 16-byte chunks per key row
+  constexpr int CPR = D / 8;    // 8-element chunks per key row (16 bytes fp16, 8 bytes e4m3)
   constexpr int NCH = KB * CPR; // chunks per block, each of K and V
   constexpr int NTH = 64 * NW;
   constexpr int CPT = NCH / NTH;
@@ -146,7 +170,8 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   // Staging: chunk i of a thread = (key ch / CPR, dims 8 (ch % CPR)) of K and
   // of V — rows coalesced, both stored row-major ([key][d]); the PV product
   // reads V transposed with ds_read_b64_tr_b16.
-  u32x4 kr[CPT], vr[CPT];
+  using Chunk = typename std::conditional<FP8, u32x2, u32x4>::type;  // 8 pool elements
+  Chunk kr[CPT], vr[CPT];
   int vok[CPT];
   auto page_of = [&](int kg) -> int {  // page of key position kg, -1 if none / past lastpos
     const int tile = kg / TS;
@@ -160,11 +185,19 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
       const int key = ch / CPR, d0 = (ch % CPR) * 8;
       const int kg = kb * KB + key;
       const int pg = page_of(kg);
-      const size_t off = (size_t)pg * a.page_stride + ((kg % TS) * D + d0) * 2;
+      const size_t off = (size_t)pg * a.page_stride + ((kg % TS) * D + d0) * ES;
       vok[i] = pg >= 0;
       // masked keys stage V = 0: a never-written row may hold NaN (0 * NaN)
-      kr[i] = pg >= 0 ? *reinterpret_cast<const u32x4*>(a.k_pool + off) : u32x4{0u, 0u, 0u, 0u};
-      vr[i] = pg >= 0 ? *reinterpret_cast<const u32x4*>(a.v_pool + off) : u32x4{0u, 0u, 0u, 0u};
+      kr[i] = pg >= 0 ? *reinterpret_cast<const Chunk*>(a.k_pool + off) : Chunk{};
+      vr[i] = pg >= 0 ? *reinterpret_cast<const Chunk*>(a.v_pool + off) : Chunk{};
+    }
+  };
+  auto as_f16 = [](const Chunk& x) -> u32x4 {  // the chunk's 8 values as fp16
+    if constexpr (FP8) {
+      const u32x2 a0 = fp8x4_to_f16(x[0]), a1 = fp8x4_to_f16(x[1]);
+      return u32x4{a0[0], a0[1], a1[0], a1[1]};
+    } else {
+      return x;
     }
   };
   auto stage = [&]() {
@@ -172,8 +205,8 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
     for (int i = 0; i < CPT; ++i) {
       const int ch = tid + i * NTH;
       const int key = ch / CPR, d0 = (ch % CPR) * 8;
-      *reinterpret_cast<u32x4*>(&Ks[key * KSTR + d0]) = kr[i];
-      *reinterpret_cast<u32x4*>(&Vs[key * VSTR + d0]) = vr[i];
+      *reinterpret_cast<u32x4*>(&Ks[key * KSTR + d0]) = as_f16(kr[i]);
+      *reinterpret_cast<u32x4*>(&Vs[key * VSTR + d0]) = as_f16(vr[i]);
       if (d0 == 0) kval[key] = vok[i];
     }
   };
@@ -264,27 +297,38 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
     } else {
       const float inv = 1.0f / (lrun + 1e-6f) * (1.0f / kPScale);
       float* o = a.out + (size_t)qi * a.out_stride + h * D + 4 * g;
+      // out_scale after the normalisation, as the merge applies it (x * 1 = x:
+      // fp16 pools keep their bits)
 #pragma unroll
-      for (int nd = 0; nd < ND; ++nd) *reinterpret_cast<f32x4*>(o + 16 * nd) = O[nd] * inv;
+      for (int nd = 0; nd < ND; ++nd)
+        *reinterpret_cast<f32x4*>(o + 16 * nd) = O[nd] * inv * a.out_scale;
     }
   }
 }
 
-template <int D, int TS>
+template <int KVT, int D, int TS>
 hipError_t launch_prefill(const PaPrefillArgs& a, int nw, hipStream_t st) {
   if (nw == 4) {
     const dim3 grid((a.m + 63) / 64, a.H, a.nsplit);
-    hipLaunchKernelGGL((pa_prefill_kernel<D, TS, 4>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 4>), grid, dim3(256), 0, st, a);
   } else {
     const dim3 grid((a.m + 31) / 32, a.H, a.nsplit);
-    hipLaunchKernelGGL((pa_prefill_kernel<D, TS, 2>), grid, dim3(128), 0, st, a);
+    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 2>), grid, dim3(128), 0, st, a);
   }
   return hipGetLastError();
 }
 
+template <int KVT>
+hipError_t launch_prefill_shape(const PaPrefillArgs& a, int D, int TS, int nw, hipStream_t st) {
+  if (D == 64)
+    return TS == 16 ? launch_prefill<KVT, 64, 16>(a, nw, st) : launch_prefill<KVT, 64, 32>(a, nw, st);
+  return TS == 16 ? launch_prefill<KVT, 128, 16>(a, nw, st) : launch_prefill<KVT, 128, 32>(a, nw, st);
+}
+
 // Launch geometry: NW waves (16 queries each) per workgroup; the key range is
 // split until the grid holds about kTargetWgs workgroups (4 per CU), in
-// splits of whole 32-key blocks and at least 2 blocks each.
+// splits of whole 32-key blocks and at least 2 blocks each.  The plan reads
+// the view's page_size and num_heads only: it is the same for fp16 and FP8 pools.
 constexpr int kTargetWgs = 1024;
 struct PrefillPlan {
   int nw, nsplit, pps;
@@ -315,7 +359,8 @@ PrefillPlan prefill_plan(const pa_kv_view* kv, int p0, int m) {
 }  // namespace
 
 bool pa_prefill_supported(const pa_kv_view* kv) {
-  return kv && kv->kv_dtype == LLM_F16 && (kv->head_dim == 64 || kv->head_dim == 128) &&
+  return kv && (kv->kv_dtype == LLM_F16 || kv->kv_dtype == LLM_FP8) &&
+         (kv->head_dim == 64 || kv->head_dim == 128) &&
          (kv->page_size == 16 || kv->page_size == 32);
 }
 
@@ -332,7 +377,8 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
   LLM_REQUIRE(kv && q, "pa_prefill: NULL argument");
   if (!pa_prefill_supported(kv))
     return fail(LLM_ERR_UNSUPPORTED,
-                "pa_prefill: fp16 pools with head_dim 64 or 128 and page_size 16 or 32 only");
+                "pa_prefill: fp16 or FP8 (e4m3) pools with head_dim 64 or 128 and page_size 16 "
+                "or 32 only");
   const int H = kv->num_heads, D = kv->head_dim, hid = H * D;
   LLM_REQUIRE(m >= 1 && p0 >= 0, "pa_prefill: need m >= 1 and p0 >= 0");
   LLM_REQUIRE(row >= 0 && row < kv->num_beams, "pa_prefill: row outside the page table");
@@ -375,17 +421,18 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
     a.nsplit = 1;
     a.pps = kv->max_tiles;
   }
-  hipError_t e;
+  // LLM_FP8 pools: the V scale (1 for fp16 pools, whatever the caller left there)
+  const float out_scale = (rows && kv->kv_dtype == LLM_FP8) ? rows->out_scale : 1.f;
+  a.out_scale = out_scale;
   const int TS = kv->page_size;
-  if (D == 64)
-    e = TS == 16 ? launch_prefill<64, 16>(a, pl.nw, st) : launch_prefill<64, 32>(a, pl.nw, st);
-  else
-    e = TS == 16 ? launch_prefill<128, 16>(a, pl.nw, st) : launch_prefill<128, 32>(a, pl.nw, st);
+  const hipError_t e = kv->kv_dtype == LLM_FP8
+                           ? launch_prefill_shape<LLM_FP8>(a, D, TS, pl.nw, st)
+                           : launch_prefill_shape<LLM_F16>(a, D, TS, pl.nw, st);
   if (e != hipSuccess) return fail(LLM_ERR_HIP, std::string("pa_prefill launch: ") + hipGetErrorString(e));
   if (split)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, (rows && !rows->keep_out) ? nullptr : out,
                                   rows, nullptr, p0, m, H, D, p0 + m, TS, pl.pps, pl.nsplit,
-                                  kv->max_tiles, st);
+                                  kv->max_tiles, st, out_scale);
   if (row_out) {  // one pass: convert the fp32 rows into the o_proj input
     if (rows->q)
       LLM_HIP_RET(launch_quantize_rows(out, m, hid, rows->q, rows->inv_scale, st, rows->pack));

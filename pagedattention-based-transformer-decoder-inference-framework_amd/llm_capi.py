@@ -60,6 +60,7 @@ _SIGS = {
     "llm_decoder_create_kv": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
     "llm_decoder_set_kv_scales": (c_int, [c_void_p, c_void_p, c_void_p]),
     "llm_decoder_kv_dtype": (c_int, [c_void_p]),
+    "llm_decoder_prefill_kernel": (c_int, [c_void_p]),
     "llm_decoder_destroy": (None, [c_void_p]),
     "llm_decoder_begin_synthetic": (c_int, [c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "pa_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
