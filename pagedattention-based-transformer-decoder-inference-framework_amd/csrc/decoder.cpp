@@ -155,7 +155,8 @@ struct llm_decoder {
   size_t b16 = 0;  // max_batch rounded up to 16-row tiles
 
   int layer_pre(int l, hipStream_t st, const struct Rows& R);
-  int layer_attn(int l, hipStream_t st, const struct Rows& R, PaPlan* plan = nullptr);
+  int layer_attn(int l, hipStream_t st, const struct Rows& R);
+  int attn_request(const struct Rows& R, pa_kv_view* view, PaRequest* rq, int l = 0);
   bool quant_prologue(const struct Rows& R) const;
   bool oproj_fusable(const struct Rows& R);
   bool wgm_quant_ok(const struct Rows& R);
@@ -559,11 +560,10 @@ bool llm_decoder::oproj_fusable(const Rows& R) {
     return false;
   Rows r = R;
   r.oacc = oacc.p;
-  r.oproj_out = R.x;
-  r.oflag = oflag.p;
-  PaPlan p;
-  if (layer_attn(0, stream, r, &p) != LLM_OK) return false;
-  return (p.form & LLM_PA_FORM_OPROJ) != 0;
+  pa_kv_view view;
+  PaRequest rq;
+  PaLaunch p;
+  return attn_request(r, &view, &rq) == LLM_OK && pa_plan_device(rq, &p) == LLM_OK && p.oproj;
 }
 
 // INT8 decode rows whose o_proj cannot quantise its own input (hidden >
@@ -578,9 +578,10 @@ bool llm_decoder::wgm_quant_ok(const Rows& R) {
     return false;
   Rows r = R;
   r.wgm_quant = true;
-  PaPlan p;
-  if (layer_attn(0, stream, r, &p) != LLM_OK) return false;
-  return (p.form & 15) == LLM_PA_FORM_WG_MERGE;
+  pa_kv_view view;
+  PaRequest rq;
+  PaLaunch p;
+  return attn_request(r, &view, &rq) == LLM_OK && pa_plan_device(rq, &p) == LLM_OK && p.wgm;
 }
 
 // INT8 decode rows <= 16 (the 4- and 8-GPU points of C3's strong curve): fc2's
@@ -600,12 +601,28 @@ bool llm_decoder::fc2_split(const Rows& R) const {
          !ln_fusable(wdtype, R.n, hid) && inter / 64 >= 16;
 }
 
-int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R, PaPlan* plan) {
+// The decode attention launch of R's rows over layer l's pages: the view of
+// the rows' page-table rows and what the launch is to return (pa_plan.hpp).
+int llm_decoder::attn_request(const Rows& R, pa_kv_view* view, PaRequest* rq, int l) {
+  RET_IF(kv_cache_view(kv, l, view));
+  view->page_table += (size_t)R.table_row0 * H * view->max_tiles;  // rows r0..
+  view->num_beams -= R.table_row0;
+  // the split merge also produces the o_proj input (packed int8 + scale, or fp16)
+  const PaOut out = quant_prologue(R) || R.wgm_quant ? PaOut::F32_ROWS  // quantised by the o_proj
+                    : wdtype == LLM_I8               ? PaOut::ROW_Q     // prologue or layer_attn
+                    : R.oacc                         ? PaOut::OPROJ
+                                                     : PaOut::ROW_F16;
+  *rq = pa_request(view, R.n, H, D, cfg.max_seq_len, pps, R.row_group, out);
+  rq->rows16 = out == PaOut::OPROJ && tap_q;  // the taps read the packed o_proj input
+  rq->steal_ctr = R.row_group >= 4 && beam_steal_on();
+  return LLM_OK;
+}
+
+int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
   pa_kv_view view;
-  RET_IF(kv_cache_view(kv, l, &view));
-  view.page_table += (size_t)R.table_row0 * H * view.max_tiles;  // rows r0..
-  view.num_beams -= R.table_row0;
-  if (R.prefill_row >= 0 && pa_prefill_supported(&view) && !plan) {
+  PaRequest rq;
+  RET_IF(attn_request(R, &view, &rq, l));
+  if (R.prefill_row >= 0 && pa_prefill_supported(&view)) {
     // one MFMA pass over the chunk (K/V pages read once per 32 queries), then
     // the o_proj input conversion the decode merge would have fused
     PaRowOutputs ro;
@@ -623,34 +640,32 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R, PaPlan* plan) 
                                kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale,
                                R.attn_ws, R.attn_ws_bytes, st, &ro);
   }
-  // the split merge also produces the o_proj input (packed int8 + scale, or fp16);
-  // the fp32 rows are only needed by a single-split (direct) launch
+  // the request's pointers; the fp32 rows (R.o) are only needed by a
+  // single-split (direct) launch, and are the output of F32_ROWS
   PaRowOutputs ro;
   ro.pack = 1;
   ro.keep_out = 0;
-  if (quant_prologue(R) || R.wgm_quant) {
-    ro.f32_rows = 1;  // fp32 rows in R.o, quantised by the o_proj prologue or the launch below
-  } else if (wdtype == LLM_I8) {
+  if (rq.out == PaOut::ROW_Q) {
     ro.q = static_cast<int8_t*>(R.act);
     ro.inv_scale = R.sa;
-  } else if (R.oacc) {
+  } else if (rq.out == PaOut::OPROJ) {
     ro.o_acc = R.oacc;
     ro.o_x = R.oproj_out;
     ro.wo_heads = wo_heads.p + (size_t)l * hid * hid;
     ro.o_n = hid;
     ro.o_flag = R.oflag;
-    ro.out16 = tap_q ? R.act : nullptr;  // the taps read the packed o_proj input
-  } else {
+    ro.out16 = rq.rows16 ? R.act : nullptr;
+  } else if (rq.out == PaOut::ROW_F16) {
     ro.out16 = R.act;
   }
-  if (R.row_group >= 4 && beam_steal_on()) ro.beam_ctr = beam_ctr.p;
+  if (rq.steal_ctr) ro.beam_ctr = beam_ctr.p;
   // LLM_FP8 pages: K's scale folded into the score multiplier, V's applied to
   // the normalised heads by the launch (1 and 1 for fp16 pages)
   ro.out_scale = v_scale[l];
-  RET_IF(pa_decode_internal(&view, R.q, hid, R.o, R.beam_rows, R.ctx, R.n, H, D, cfg.max_seq_len,
-                            kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale, pps,
-                            R.attn_ws, R.attn_ws_bytes, st, &ro, R.row_group, plan));
-  if (R.wgm_quant && !plan)  // the packed int8 o_proj input + row scales
+  RET_IF(pa_decode_internal(&view, rq, R.q, hid, R.o, R.beam_rows, R.ctx,
+                            kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale,
+                            R.attn_ws, R.attn_ws_bytes, st, &ro));
+  if (R.wgm_quant)  // the packed int8 o_proj input + row scales
     LLM_HIP_RET(launch_quantize_rows(R.o, R.n, hid, static_cast<int8_t*>(R.act), R.sa, st, 1));
   return LLM_OK;
 }
@@ -1093,10 +1108,14 @@ extern "C" int llm_decoder_attention_plan(llm_decoder* d, int* nsplit, int* form
   Rows R = d->step_rows(0, d->batch, d->attn_ws.p);
   if (d->oproj_fusable(R)) R.oacc = d->oacc.p, R.oproj_out = R.x, R.oflag = d->oflag.p;
   R.wgm_quant = d->wgm_quant_ok(R);
-  PaPlan p;
-  RET_IF(d->layer_attn(0, d->stream, R, &p));
+  pa_kv_view view;
+  PaRequest rq;
+  PaLaunch p;
+  RET_IF(d->attn_request(R, &view, &rq));
+  RET_IF(pa_decode_internal(&view, rq, nullptr, d->hid, nullptr, nullptr, nullptr, 1.f, nullptr, 0,
+                            nullptr, nullptr, &p));
   *nsplit = p.nsplit;
-  *form = p.form;
+  *form = p.form();
   return LLM_OK;
 }
 

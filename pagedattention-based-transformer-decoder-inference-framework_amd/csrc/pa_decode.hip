@@ -1,10 +1,11 @@
-// Paged decode attention for gfx950 (CDNA4): launch planning (split counts,
-// forms), the split merges and the C entry points (pa_decode,
-// pa_decode_grouped, pa_decode_plan).  The split kernel itself, and the design
-// notes of the scan, are in pa_split.hpp; the tuning build's experiment
-// kernels and A/B entry are in csrc/tune/pa_decode_tune.hip.
+// Paged decode attention for gfx950 (CDNA4): the split merges, the launch of a
+// plan (pa_decode_internal: validate, plan, fill PaSplitArgs, launch, merge)
+// and the C entry points (pa_decode, pa_decode_grouped, pa_decode_plan).  The
+// plan itself (split counts, forms) is pa_plan.hpp's, host-only; the split
+// kernel, its named forms and the design notes of the scan are in
+// pa_split.hpp; the tuning build's experiment kernels and A/B entries are in
+// csrc/tune/pa_decode_tune.hip.
 #include "pa_split.hpp"
-#include "pa_tuning.hpp"
 
 namespace llm {
 
@@ -215,39 +216,52 @@ __global__ __launch_bounds__(1024) void pa_merge_row_kernel(PaMergeRowArgs a) {
 
 namespace {
 
-constexpr int kMinPps = 8;
-constexpr int kMaxWavesPerCu = 32;  // 8 per SIMD x 4 SIMDs (gfx950)
-
-// Resident waves of the whole chip for one split-kernel instantiation
-// (occupancy query x CU count), cached.  Fallback: 256 CUs x 3 waves/SIMD.
-// Register stages of an instantiation: pages above 8 KiB hold a whole stage
-// per page already (two would not fit the VGPR file).
-template <int D, int TS, int KVT>
-constexpr int split_stages() {
-  return TS * D * kv_elem_bytes<KVT>() > 8192 ? 1 : 2;
+// Resident waves of the whole chip for a 256-thread kernel (its occupancy x
+// the CU count); 0 where the query fails.  occupancy(&blocks) -> hipError_t.
+template <class Q>
+long long chip_waves(Q&& occupancy) {
+  int dev = 0, cus = 0, blocks = 0;
+  if (hipGetDevice(&dev) == hipSuccess &&
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+      occupancy(&blocks) == hipSuccess && cus > 0 && blocks > 0)
+    return (long long)cus * blocks * 4;
+  (void)hipGetLastError();
+  return 0;
 }
 
-template <int D, int TS, bool DIRECT, int KVT>
+// ... of the plain split kernel of one shape, cached (kFallbackResident
+// without a device), and of the beam-group form (0 where the plain schedule
+// runs instead: pages above 8 KiB).
+template <int D, int TS, int KVT>
 long long resident_waves() {
   static long long cached = 0;
   if (cached) return cached;
-  int dev = 0, cus = 0, blocks = 0;
-  constexpr int ST = split_stages<D, TS, KVT>();
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &blocks, pa_split_kernel<D, TS, DIRECT, 16384, kKvLoadAux, ST, 0, false, false, KVT>, 256,
-          0) == hipSuccess &&
-      cus > 0 && blocks > 0) {
-    cached = (long long)cus * blocks * 4;
-  } else {
-    (void)hipGetLastError();
-    cached = 256LL * 4 * 3;
-  }
+  cached = chip_waves([](int* blocks) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks, pa_split_kernel<D, TS, pa_cfg_split(D, TS, KVT)>, 256, 0);
+  });
+  if (!cached) cached = kFallbackResident;
   return cached;
 }
 
+template <int D, int TS>
+long long beam_resident_waves() {
+  if constexpr (split_stages(D, TS, 2) != 2) {
+    return 0;
+  } else {
+    static long long cached = -1;
+    if (cached >= 0) return cached;
+    return cached = chip_waves([](int* blocks) {
+      hipError_t e;
+      if (tune_beam_occupancy(D, TS, blocks, &e)) return e;
+      return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          blocks, pa_split_kernel<D, TS, pa_cfg_beam()>, 256, 0);
+    });
+  }
+}
+
 }  // namespace
+
 
 // The FP16 decoder's o_proj fused into the workgroup merge (decoder.cpp
 // oproj_fusable); LLM_OPROJ_FUSE=0 (tuning build) restores the o_proj GEMM.
@@ -264,212 +278,81 @@ namespace {
 // 82.3 at 12 splits, against 67.6 us; MFMA 69.8 vs 60.8 us; steal 76-92 vs
 // 65.3 us).
 
-// LLM_FP8 pools merge in the workgroup for pages up to 2 KiB (64 or 128 dims x
-// 16 tokens, 64 x 32: C3's and C5's shape among them).  Larger pages hold more
-// decoded elements live per stage than the form's 512-thread bound (256 VGPRs)
-// leaves room for -- 128 x 32 and 256 x 16 spill 76-80 bytes per lane, 256 x 32
-// 224 -- so they keep split + merge.
-constexpr bool fp8_wgm_shape_ok(int D, int TS) { return D * TS <= 2048; }
-
-template <int D, int TS, int KVT>
-hipError_t launch_split(const PaSplitArgs& a, bool direct, hipStream_t st, bool* beam) {
-  const int waves = ((a.B + a.group - 1) / a.group) * a.group * a.H * a.nsplit;
-  const dim3 grid((waves + 3) / 4), block(256);
-  if constexpr (KVT != LLM_F16) {
-    // other KV element types: the standard schedule (no beam-prefetch form)
-    constexpr int ST = split_stages<D, TS, KVT>();
-    if constexpr (KVT == LLM_FP8 && fp8_wgm_shape_ok(D, TS)) {
-      // the decoder's own forms: the workgroup merge as well (no fused o_proj:
-      // pa_decode_internal refuses o_acc with these pools)
-      if (a.wgm) {
-        hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST, 0, false, false,
-                                            LLM_FP8, true, true>),
-                           dim3(a.B * a.H), dim3(64 * a.nsplit), 0, st, a);
-        return hipGetLastError();
-      }
-    }
-    if (direct)
-      hipLaunchKernelGGL((pa_split_kernel<D, TS, true, 16384, kKvLoadAux, ST, 0, false, false, KVT>),
-                         grid, block, 0, st, a);
-    else
-      hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST, 0, false, false, KVT>),
-                         grid, block, 0, st, a);
-    return hipGetLastError();
-  }
-  constexpr int ST = split_stages<D, TS, LLM_F16>();
-  if (a.wgm) {  // pa_decode_internal: group 1, 2..8 splits, not direct
-    if constexpr (D <= kOprojMaxD) {
-      if (a.o_acc) {
-        hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST, 0, false, false,
-                                            LLM_F16, true, true, true>),
-                           dim3(a.B * a.H), dim3(64 * a.nsplit), 0, st, a);
-        return hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST, 0, false, false,
-                                        LLM_F16, true, true>),
-                       dim3(a.B * a.H), dim3(64 * a.nsplit), 0, st, a);
-    return hipGetLastError();
-  }
-  if (a.group == 4 && !direct && ST == 2) {
-    // 8 KiB register stages: 112 VGPRs, 4 waves per SIMD.  The 16 KiB form
-    // (179 VGPRs, 2 waves) spent 27 % of its wave time in issue stalls and
-    // 20 % parked (SQ PMC, scripts/gpu_sq_pmc.sh); same-box A/B of the C4
-    // launch: 72-74 vs 76 us (scripts/ab_attention_lib.py, -DLLM_BEAM_CHUNK=)
-#ifndef LLM_BEAM_CHUNK
-#define LLM_BEAM_CHUNK 8192
-#define LLM_BEAM_WAVES 0
-#endif
-    hipError_t te;
-    if (tune_launch_form(a, D, TS, grid, st, &te)) {  // tuning build: an experiment form
-      *beam = true;
-      return te;
-    }
-    hipLaunchKernelGGL((pa_split_kernel<D, TS, false, LLM_BEAM_CHUNK, kKvLoadAux, 2, LLM_BEAM_WAVES,
-                                        false, true, LLM_F16, true, false, false, 0, false, true, true>),
-                       grid, block, 0, st, a);
-    *beam = true;
-  } else if (direct) {
-    hipLaunchKernelGGL((pa_split_kernel<D, TS, true, 16384, kKvLoadAux, ST>), grid, block, 0, st, a);
-  } else {
-    hipLaunchKernelGGL((pa_split_kernel<D, TS, false, 16384, kKvLoadAux, ST>), grid, block, 0, st, a);
-  }
+template <int D, int TS, PaSplitCfg C>
+hipError_t launch_form(const PaSplitArgs& a, dim3 grid, dim3 block, hipStream_t st) {
+  hipLaunchKernelGGL((pa_split_kernel<D, TS, C>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 
-template <int D, int KVT>
-hipError_t dispatch_ts(const PaSplitArgs& a, int TS, bool direct, hipStream_t st, bool* beam) {
-  constexpr int ES = kv_elem_bytes<KVT>();
-  if (TS == 16) {
-    if constexpr (kv_shape_ok(D, 16, ES)) return launch_split<D, 16, KVT>(a, direct, st, beam);
-  } else if (TS == 32) {
-    if constexpr (kv_shape_ok(D, 32, ES)) return launch_split<D, 32, KVT>(a, direct, st, beam);
+// The split launch of a plan, in the form the plan names.
+template <int D, int TS, int KVT>
+hipError_t launch_split(const PaSplitArgs& a, const PaLaunch& p, hipStream_t st) {
+  const int waves = ((a.B + a.group - 1) / a.group) * a.group * a.H * a.nsplit;
+  const dim3 grid((waves + 3) / 4), block(256);
+  if (p.wgm) {  // one workgroup per (b, h), one wave per split (2..8)
+    const dim3 wgrid(a.B * a.H), wblock(64 * a.nsplit);
+    if constexpr (KVT == LLM_F16) {
+      if constexpr (D <= kOprojMaxD) {
+        if (p.oproj) return launch_form<D, TS, pa_cfg_wgm_oproj(D, TS)>(a, wgrid, wblock, st);
+      }
+      return launch_form<D, TS, pa_cfg_wgm(D, TS)>(a, wgrid, wblock, st);
+    } else if constexpr (KVT == LLM_FP8 && fp8_wgm_shape_ok(D, TS)) {
+      // the decoder's own forms: the workgroup merge as well (no fused o_proj:
+      // the planner keeps o_proj and fp16 rows to fp16 pools)
+      return launch_form<D, TS, pa_cfg_wgm_fp8(D, TS)>(a, wgrid, wblock, st);
+    } else {
+      return hipErrorInvalidValue;  // (no plan: other pools keep split + merge)
+    }
   }
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-hipError_t dispatch_kvt(const PaSplitArgs& a, int kvt, int TS, bool direct, hipStream_t st,
-                        bool* beam) {
-  switch (kvt) {
-    case LLM_F16: return dispatch_ts<D, LLM_F16>(a, TS, direct, st, beam);
-    case LLM_BF16: return dispatch_ts<D, LLM_BF16>(a, TS, direct, st, beam);
-    case LLM_F32: return dispatch_ts<D, LLM_F32>(a, TS, direct, st, beam);
-    case LLM_I8: return dispatch_ts<D, LLM_I8>(a, TS, direct, st, beam);
-    case LLM_FP8: return dispatch_ts<D, LLM_FP8>(a, TS, direct, st, beam);
-    default: return hipErrorInvalidValue;
+  // other KV element types than fp16: the standard schedule (no beam-prefetch form)
+  if constexpr (KVT == LLM_F16) {
+    if (p.beam) {
+      hipError_t te;
+      if (tune_launch_form(a, D, TS, grid, st, &te)) return te;  // tuning build: an experiment form
+      return launch_form<D, TS, pa_cfg_beam()>(a, grid, block, st);
+    }
   }
-}
-
-int kv_dtype_bytes(int kvt) {
-  switch (kvt) {
-    case LLM_F16: case LLM_BF16: return 2;
-    case LLM_F32: return 4;
-    case LLM_I8: case LLM_FP8: return 1;
-    default: return 0;
-  }
+  if (p.direct) return launch_form<D, TS, pa_cfg_split(D, TS, KVT, true)>(a, grid, block, st);
+  return launch_form<D, TS, pa_cfg_split(D, TS, KVT)>(a, grid, block, st);
 }
 
 bool supported(int D, int TS, int kvt) {
-  const int es = kv_dtype_bytes(kvt);
-  return es > 0 && (D == 32 || D == 64 || D == 128 || D == 256) && (TS == 16 || TS == 32) &&
-         kv_shape_ok(D, TS, es);
-}
-
-// Upper bound of the split count of any launch over rows of <= ntiles tiles
-// (workspace sizing; host-only, no device query).
-long long max_nsplit(int B, int H, int ntiles) {
-  ntiles = std::max(ntiles, 1);
-  const long long bh = std::max(1LL, (long long)B * H);
-  const long long cap = 256LL * kMaxWavesPerCu;  // largest resident-wave count
-  const long long lo = (ntiles + kMaxPps - 1) / kMaxPps;
-  return std::min<long long>(
-      kMaxSplits,
-      std::max(lo, std::min<long long>((ntiles + kMinPps - 1) / kMinPps, lo + (cap + bh - 1) / bh + 1)));
-}
-
-// Splits per (b, h): the smallest NS that is a whole number of resident-wave
-// rounds (B*H*NS ~ k * resident) with splits of <= kMaxPps pages, so every wave
-// carries the same page count and the last round is not a ragged tail; never
-// below kMinPps pages per split.  Small launches, where a full round would
-// leave each wave under kShortPps pages, use fewer, longer splits instead,
-// as long as at least kMinLaunchWaves waves remain: a split's fixed cost
-// (page ids, q, its partial and its share of the merge) outweighs an idle
-// part of the chip there.  Measured (scripts/sweep_attention_pps.py), round
-// rule -> this rule: C2 (16 x 12 heads, 2048 tokens) 25.1 -> 21.3 us;
-// 64 x 12 x 2048: 72.7 -> 66.6 us; 8 x 16 x 4096: 49.3 -> 46.1 us;
-// 1 x 16 x 8192: 32.8 -> 26.4 us; 4 x 12 x 1024 unchanged (9.9 us).
-constexpr int kShortPps = 32;
-constexpr long long kMinLaunchWaves = 512;
-// Workgroup-merge launches (PaSplitArgs::wgm) have no merge launch to feed, so
-// their splits stay long: C2 (130 tiles) 3 splits, not 5.  Same-box C2 sweep
-// (scripts/gpu_wgm_splits.sh, forced splits 2 / 3 / 4 / 5 / 6 / 8):
-// 27.4-28.0k / 29.6-30.1k / 29.1-29.2k / 28.4k / 28.6-28.9k / 28.2-29.0k tok/s.
-constexpr int kWgmShortPps = 64;
-int choose_nsplit(int B, int H, int ntiles, int pps_fixed, long long resident,
-                  int short_pps = kShortPps) {
-  ntiles = std::max(ntiles, 1);
-  if (pps_fixed > 0) {
-    const int pps = std::min(pps_fixed, kMaxPps);
-    return (ntiles + pps - 1) / pps;
-  }
-  const long long bh = std::max(1LL, (long long)B * H);
-  const long long lo = (ntiles + kMaxPps - 1) / kMaxPps;
-  long long ns = lo;
-  for (long long k = 1; k <= 64; ++k) {
-    const long long cand = (k * resident + bh - 1) / bh;
-    if (cand >= lo) { ns = cand; break; }
-  }
-  ns = std::min<long long>(ns, std::max(1, (ntiles + kMinPps - 1) / kMinPps));
-  if ((ntiles + ns - 1) / ns < short_pps)
-    ns = std::min(ns, std::max<long long>((ntiles + short_pps - 1) / short_pps,
-                                          (kMinLaunchWaves + bh - 1) / bh));
-  ns = std::max(ns, lo);
-  return (int)std::min(ns, max_nsplit(B, H, ntiles));
-}
-
-template <int D, int TS, int KVT>
-long long resident_for() {
-  if constexpr (kv_shape_ok(D, TS, kv_elem_bytes<KVT>()))
-    return resident_waves<D, TS, false, KVT>();
-  return 256LL * 4 * 3;
-}
-
-template <int D>
-long long resident_for_kvt(int TS, int kvt) {
-  auto by_ts = [&](auto k) -> long long {
-    constexpr int K = decltype(k)::value;
-    return TS == 16 ? resident_for<D, 16, K>() : resident_for<D, 32, K>();
-  };
-  switch (kvt) {
-    case LLM_BF16: return by_ts(std::integral_constant<int, LLM_BF16>{});
-    case LLM_F32: return by_ts(std::integral_constant<int, LLM_F32>{});
-    case LLM_I8: return by_ts(std::integral_constant<int, LLM_I8>{});
-    case LLM_FP8: return by_ts(std::integral_constant<int, LLM_FP8>{});
-    default: return by_ts(std::integral_constant<int, LLM_F16>{});
-  }
-}
-
-long long resident_waves_for(int D, int TS, int kvt) {
-  auto pick = [&](auto d) -> long long {
-    constexpr int DD = decltype(d)::value;
-    return resident_for_kvt<DD>(TS, kvt);
-  };
-  switch (D) {
-    case 32: return pick(std::integral_constant<int, 32>{});
-    case 64: return pick(std::integral_constant<int, 64>{});
-    case 128: return pick(std::integral_constant<int, 128>{});
-    default: return pick(std::integral_constant<int, 256>{});
-  }
+  return pa_for_shape(D, TS, kvt, false, [](auto, auto, auto) { return true; });
 }
 
 }  // namespace
 
+int pa_plan_device(const PaRequest& rq, PaLaunch* launch, long long resident,
+                   long long beam_resident, long long beam4_resident) {
+  *launch = PaLaunch{};
+  const int D = rq.D, TS = rq.TS;
+  if (!supported(D, TS, rq.kv_dtype)) return LLM_ERR_UNSUPPORTED;
+  const PaTuning tn = pa_tuning();
+  const bool beam_group = rq.row_group == 4 && rq.kv_dtype == LLM_F16;
+  if (rq.pps_fixed > 0) {  // fixed splits are sized without the chip
+    resident = beam_resident = beam4_resident = 0;
+  } else {
+    if (resident < 0)
+      resident = pa_for_shape(D, TS, rq.kv_dtype, kFallbackResident, [](auto d, auto ts, auto k) {
+        return resident_waves<decltype(d)::value, decltype(ts)::value, decltype(k)::value>();
+      });
+    if (beam_resident < 0)
+      beam_resident = !beam_group ? 0 : pa_for_shape(D, TS, LLM_F16, 0LL, [](auto d, auto ts, auto) {
+        return beam_resident_waves<decltype(d)::value, decltype(ts)::value>();
+      });
+    if (beam4_resident < 0)
+      beam4_resident = beam_group && tn.beam4 && !tn.beam_mfma && split_stages(D, TS, 2) == 2
+                           ? tune_beam4_resident_for(D, TS) : 0;
+  }
+  return pa_plan(rq, tn, resident, beam_resident, beam4_resident, launch);
+}
+
 int pa_pages_per_split(int B, int H, int T, int TS, int max_tiles) {
   const int ntiles = std::max(1, std::min((T + TS - 1) / TS, max_tiles));
-  const int ns = choose_nsplit(B, H, ntiles, 0, 256LL * 4 * 3);
+  const int ns = choose_nsplit(B, H, ntiles, 0, kFallbackResident);
   return (ntiles + ns - 1) / ns;
 }
+
 
 }  // namespace llm
 
@@ -526,195 +409,59 @@ int llm::pa_merge_rows_internal(const float* part_acc, const float* part_ml, flo
   return LLM_OK;
 }
 
-namespace {
-template <int D, int TS>
-hipError_t beam_occupancy(int* blocks) {
-  hipError_t e;
-  if (tune_beam_occupancy(D, TS, blocks, &e)) return e;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      blocks, pa_split_kernel<D, TS, false, LLM_BEAM_CHUNK, kKvLoadAux, 2, LLM_BEAM_WAVES, false, true,
-                              LLM_F16, true, false, false, 0, false, true, true>,
-      256, 0);
-}
-
-// Resident waves of the beam-group kernel (0 where the plain schedule runs
-// instead: pages above 8 KiB).
-template <int D, int TS>
-long long beam_resident_waves() {
-  if constexpr (!kv_shape_ok(D, TS, 2) || split_stages<D, TS, LLM_F16>() != 2) {
-    return 0;
-  } else {
-    static long long cached = -1;
-    if (cached >= 0) return cached;
-    int dev = 0, cus = 0, blocks = 0;
-    cached = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        beam_occupancy<D, TS>(&blocks) == hipSuccess &&
-        cus > 0 && blocks > 0)
-      cached = (long long)cus * blocks * 4;
-    else
-      (void)hipGetLastError();
-    return cached;
-  }
-}
-
-long long beam_resident_waves_for(int D, int TS) {
-  auto by_ts = [&](auto d) -> long long {
-    constexpr int DD = decltype(d)::value;
-    return TS == 16 ? beam_resident_waves<DD, 16>() : beam_resident_waves<DD, 32>();
-  };
-  switch (D) {
-    case 32: return by_ts(std::integral_constant<int, 32>{});
-    case 64: return by_ts(std::integral_constant<int, 64>{});
-    case 128: return by_ts(std::integral_constant<int, 128>{});
-    default: return by_ts(std::integral_constant<int, 256>{});
-  }
-}
-}  // namespace
-
-int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
-                            const int32_t* beam_ids, const int32_t* context_lens, int B, int H,
-                            int D, int T, float sm_scale, int pages_per_split, void* workspace,
-                            size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows,
-                            int row_group, PaPlan* plan) {
+int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const float* q, int q_stride,
+                            float* out, const int32_t* beam_ids, const int32_t* context_lens,
+                            float sm_scale, void* workspace, size_t workspace_bytes,
+                            hipStream_t st, const PaRowOutputs* rows, PaLaunch* plan) {
+  const int B = rq.B, H = rq.H, D = rq.D, T = rq.T;
   LLM_REQUIRE(kv != nullptr, "pa_decode: kv view is NULL");
   LLM_REQUIRE(B >= 0 && H > 0 && D > 0 && T >= 0, "pa_decode: bad B/H/D/T");
-  if (plan) *plan = PaPlan{};
+  if (plan) *plan = PaLaunch{};
   if (B == 0) return LLM_OK;
-  const bool row_out = rows && (rows->q || rows->out16);
   // the FP16 decoder's fused o_proj (PaRowOutputs::o_acc): workgroup-merge launches only
-  const bool oproj = rows && rows->o_acc && !rows->q && !rows->f32_rows;
+  const bool oproj = rq.out == PaOut::OPROJ, f32_rows = rq.out == PaOut::F32_ROWS;
+  const bool out16 = rq.out == PaOut::ROW_F16 || (oproj && rq.rows16);
+  const bool row_out = rq.out == PaOut::ROW_Q || out16;
   LLM_REQUIRE(plan || (q != nullptr && (out != nullptr || row_out || oproj)), "pa_decode: q/out NULL");
-  LLM_REQUIRE(!oproj || (rows->wo_heads && rows->o_x && rows->o_flag && rows->o_n > 0 &&
-                         D <= kOprojMaxD && H <= 64),
+  LLM_REQUIRE(plan || rq.out == PaOut::F32 || f32_rows || rows, "pa_decode: row outputs need PaRowOutputs");
+  LLM_REQUIRE(!oproj || (D <= kOprojMaxD && H <= 64 &&
+                         (plan || (rows->o_acc && rows->wo_heads && rows->o_x && rows->o_flag &&
+                                   rows->o_n > 0))),
               "pa_decode: fused o_proj needs W_o head slices, an output, a range flag, o_n > 0, "
               "head_dim <= 128 and at most 64 heads");
-  LLM_REQUIRE(!rows || !rows->q || rows->inv_scale, "pa_decode: row quantisation needs inv_scale");
+  LLM_REQUIRE(plan || rq.out != PaOut::ROW_Q || (rows->q && rows->inv_scale),
+              "pa_decode: row quantisation needs q and inv_scale");
+  LLM_REQUIRE(plan || !out16 || rows->out16, "pa_decode: fp16 rows need out16");
   LLM_REQUIRE(!row_out || (size_t)H * D * 4 <= 65536, "pa_decode: row outputs need H*D <= 16384");
   LLM_REQUIRE(!rows || !rows->pack || (H * D) % 64 == 0, "pa_decode: packed row outputs need H*D % 64 == 0");
   LLM_REQUIRE(kv->k_pool && kv->v_pool && kv->page_table, "pa_decode: kv pointers NULL");
-  LLM_REQUIRE(kv_dtype_bytes(kv->kv_dtype) > 0,
+  LLM_REQUIRE(kv_elem_size(kv->kv_dtype) > 0,
               "pa_decode: kv_dtype must be LLM_F16, LLM_BF16, LLM_F32, LLM_I8 or LLM_FP8");
   LLM_REQUIRE(kv->num_heads == H, "pa_decode: H != kv->num_heads");
   LLM_REQUIRE(kv->head_dim == D, "pa_decode: D != kv->head_dim");
   LLM_REQUIRE(kv->num_pages > 0 && kv->num_beams > 0 && kv->max_tiles > 0,
               "pa_decode: empty kv view");
+  LLM_REQUIRE(rq.TS == kv->page_size && rq.max_tiles == kv->max_tiles && rq.kv_dtype == kv->kv_dtype,
+              "pa_decode: the request is not of this kv view (pa_request)");
   if (!supported(D, kv->page_size, kv->kv_dtype))
     return fail(LLM_ERR_UNSUPPORTED, "pa_decode: unsupported head_dim/page_size/kv_dtype (D in "
                                      "{32,64,128,256}, page_size in {16,32}, one page of "
                                      "1..16 KiB)");
   const size_t page_stride = kv_view_page_stride(*kv);
-  LLM_REQUIRE(page_stride >= (size_t)kv->page_size * D * kv_dtype_bytes(kv->kv_dtype) &&
+  LLM_REQUIRE(page_stride >= (size_t)kv->page_size * D * kv_elem_size(kv->kv_dtype) &&
                   page_stride % 16 == 0,
               "pa_decode: page_stride must be 0 or >= one page and a multiple of 16");
   LLM_REQUIRE((long long)kv->num_pages * (long long)page_stride < (1LL << 47),
               "pa_decode: pool too large");
   const int TS = kv->page_size;
-  // tiles at or past max_tiles have no page-table entry: they are missing (masked)
-  const int ntiles_max = std::max(1, std::min((T + TS - 1) / TS, kv->max_tiles));
-  const int pps_fixed = pages_per_split > 0 ? std::min(pages_per_split, kMaxPps) : 0;
-  const long long resident = pps_fixed <= 0 ? resident_waves_for(D, TS, kv->kv_dtype) : 0;
-  // beam-group launches size their splits for the beam kernel's occupancy
-  // (4 waves per SIMD against the plain kernel's 2: C4 8 splits, not 4)
-  const long long resident_launch =
-      pps_fixed <= 0 && row_group == 4 && kv->kv_dtype == LLM_F16
-          ? std::max(resident, beam_resident_waves_for(D, TS)) : resident;
-  // fp16 o_proj input only (the FP16 decoder's attention): with at most one
-  // merge batch of splits per (b, h) the splits merge inside the split
-  // launch's workgroup (C2: 12 merge launches per step fewer), with long splits
-  // fp32 rows for a quantising consumer (the INT8 decoder's o_proj prologue)
-  // merge in the workgroup too, with a split count that divides the CU's 8
-  // resident waves (2 / 4 / 8 waves per workgroup: a 6-wave workgroup would
-  // leave 2 of the 8 slots idle): C3 6 -> 8 splits
-  const bool f32_rows = rows && rows->f32_rows && !rows->q && !rows->out16;
-  const PaTuning tn = pa_tuning();
-  int nsplit = choose_nsplit(B, H, ntiles_max, pps_fixed, resident_launch);
-  // fp32 rows whose launch is exactly one resident round of more splits than
-  // a workgroup merge holds (C3's model at 8 rows per GPU: 128 (row, head)
-  // pairs x 16 splits of 33 pages = 2,048 waves): half the splits, twice as
-  // long, still split + merge.  Standalone (scripts/tune_attention.py --B 8,
-  // profiles/r05/attention_b8_split_sweep.txt): 85.6 -> 84.3 us, the
-  // loads-only form 83.7 / 83.4 us at either count.
-  const bool half_round = f32_rows && row_group == 1 && pps_fixed <= 0 &&
-                          (kv->kv_dtype == LLM_F16 || kv->kv_dtype == LLM_FP8) &&
-                          nsplit > kWgmMaxSplits &&
-                          (long long)B * H * nsplit == resident_launch &&
-                          (ntiles_max + nsplit - 1) / nsplit <= 2 * kShortPps;
-  if (half_round) nsplit = (nsplit + 1) / 2;
-  // fp16 pools, and fp8 pools for the fp32-row merge (the INT8 decoder's): the
-  // fused o_proj and the fp16 row output of the workgroup merge are fp16-KV
-  // forms, so an FP16-weights decoder on fp8 pages runs split + merge-row
-  const bool wgm_kvt = kv->kv_dtype == LLM_F16 ||
-                       (kv->kv_dtype == LLM_FP8 && !oproj && !(rows && rows->out16) &&
-                        fp8_wgm_shape_ok(D, TS));
-  const bool wgm_ok = ((row_out && rows->out16 && !rows->q) || oproj || f32_rows) && row_group == 1 &&
-                      wgm_kvt && tn.wg_merge && !half_round;
-  if (wgm_ok && pps_fixed <= 0 && !f32_rows) {
-    const int nw = choose_nsplit(B, H, ntiles_max, 0, resident_launch, kWgmShortPps);
-    if (nw >= 2 && nw <= kWgmMaxSplits) nsplit = nw;
-  }
-  if (wgm_ok && pps_fixed <= 0 && f32_rows && nsplit >= 2) {
-    int nw = 2;
-    while (nw < nsplit && nw < kWgmMaxSplits) nw *= 2;
-    if (nw >= nsplit && (long long)nw * kMaxPps >= ntiles_max) nsplit = nw;
-  }
-  // tuning build: forced split counts of beam-group launches and of the
-  // workgroup-merge eligible ones (fp16 row outputs, dynamic splits)
-  if (row_group == 4 && pps_fixed <= 0) {
-    const int f = tn.beam_nsplit;
-    if (f >= 2 && (long long)f * kMaxPps >= ntiles_max) nsplit = std::min(f, kMaxSplits);
-  }
-  if (rows && (rows->out16 || oproj || f32_rows) && !rows->q && row_group == 1 && pps_fixed <= 0) {
-    const int f = tn.wgm_splits;
-    if (f >= 2 && f <= kWgmMaxSplits && (long long)f * kMaxPps >= ntiles_max) nsplit = f;
-  }
-  // beam groups of 4 rows (fp16 pages <= 8 KiB, dynamic splits): pa_beam4_kernel,
-  // one wave per (group, head, split), splits sized for its own occupancy (a
-  // whole number of resident rounds over (group, head) pairs), each split
-  // holding <= 128 page items; fixed pages_per_split keeps the BEAM form
-  bool use_beam4 = false;
-  if (row_group == 4 && pps_fixed <= 0 && kv->kv_dtype == LLM_F16 && TS * D * 2 <= 8192 &&
-      tn.beam4 && !tn.beam_mfma) {
-    const long long groups = (long long)((B + 3) / 4) * H;
-    const long long need = (4LL * ntiles_max + kMaxPps - 1) / kMaxPps;
-    long long ns = (tune_beam4_resident_for(D, TS) + groups - 1) / groups;
-    ns = std::max(std::max(ns, need), 2LL);
-    ns = std::min(ns, max_nsplit(B, H, ntiles_max));
-    if (tn.beam4_splits >= 2) ns = std::min<long long>(tn.beam4_splits, max_nsplit(B, H, ntiles_max));
-    if (ns >= need && ns >= 2) {
-      use_beam4 = true;
-      nsplit = (int)ns;
-    }
-  }
-  if (nsplit > kMaxSplits || (long long)nsplit * (pps_fixed > 0 ? pps_fixed : kMaxPps) < ntiles_max)
+  PaLaunch p;
+  if (pa_plan_device(rq, &p) != LLM_OK)
     return fail(LLM_ERR_UNSUPPORTED,
                 "pa_decode: at most 128 splits of at most 128 pages per row (raise "
                 "pages_per_split, or pass 0; T <= 16384 pages)");
-  const bool direct = nsplit <= 1;
-  // beam groups of 4 fp16 rows with counters: dynamic tile assignment
-  const bool steal_form = tn.beam_steal && row_group >= 4 && !direct &&
-                          kv->kv_dtype == LLM_F16 && pps_fixed <= 0 && !use_beam4 &&
-                          !tn.beam_mfma && steal_shape_ok(D, TS);
-  if (plan) {
-    const int group = std::max(1, std::min(row_group, 4));
-    const bool wg = wgm_ok && !direct && group == 1 && nsplit <= kWgmMaxSplits;
-    const bool beam = group == 4 && !direct && kv->kv_dtype == LLM_F16 &&
-                      TS * D * 2 <= 8192;
-    const bool steal = steal_form && rows && rows->beam_ctr;
-    plan->nsplit = nsplit;
-    plan->form = (direct ? LLM_PA_FORM_DIRECT : wg ? LLM_PA_FORM_WG_MERGE
-                  : row_out ? LLM_PA_FORM_SPLIT_MERGE_ROW : LLM_PA_FORM_SPLIT_MERGE) |
-                 (beam ? LLM_PA_FORM_BEAM : 0) | (oproj && wg ? LLM_PA_FORM_OPROJ : 0) |
-                 (steal ? LLM_PA_FORM_STEAL : 0);
-    return LLM_OK;
-  }
-  unsigned* steal_ctr = nullptr;
-  if (steal_form)
-    steal_ctr = rows && rows->beam_ctr ? rows->beam_ctr
-                                       : tune_steal_counters(2 * (size_t)((B + 3) / 4) * H);
-  LLM_REQUIRE(!direct || out != nullptr, "pa_decode: single-split launch needs the fp32 out");
-  if (oproj && (direct || row_group != 1 || nsplit > kWgmMaxSplits || !wgm_ok))
+  if (plan) return *plan = p, LLM_OK;
+  LLM_REQUIRE(!p.direct || out != nullptr, "pa_decode: single-split launch needs the fp32 out");
+  if (oproj && !p.oproj)
     return fail(LLM_ERR_UNSUPPORTED,
                 "pa_decode: the fused o_proj needs the workgroup-merge form over fp16 pools");
 
@@ -722,70 +469,56 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, 
   a.k_pool = static_cast<const uint8_t*>(kv->k_pool);
   a.v_pool = static_cast<const uint8_t*>(kv->v_pool);
   a.page_table = kv->page_table;
-  a.q = q;
-  a.q_stride = q_stride;
-  a.out = out;
-  a.beam_ids = beam_ids;
-  a.context_lens = context_lens;
-  a.B = B;
-  a.H = H;
-  a.T = T;
-  a.num_pages = kv->num_pages;
-  a.num_beams = kv->num_beams;
-  a.max_tiles = kv->max_tiles;
+  a.q = q, a.q_stride = q_stride, a.out = out;
+  a.beam_ids = beam_ids, a.context_lens = context_lens;
+  a.B = B, a.H = H, a.T = T;
+  a.num_pages = kv->num_pages, a.num_beams = kv->num_beams, a.max_tiles = kv->max_tiles;
   a.page_stride = page_stride;
-  a.pps = pps_fixed;
-  a.nsplit = nsplit;
-  a.group = std::max(1, std::min(row_group, 4));
+  a.pps = p.pps, a.nsplit = p.nsplit, a.group = std::max(1, std::min(rq.row_group, 4));
   a.qscale = sm_scale * kLog2e;
   const float out_scale = rows && kv->kv_dtype == LLM_FP8 ? rows->out_scale : 1.f;
   a.out_scale = out_scale;
-  const bool wgm = wgm_ok && !direct && a.group == 1 && nsplit <= kWgmMaxSplits;
-  if (!direct && !wgm) {  // (the workgroup merge keeps its splits' states in LDS)
-    const size_t need = (size_t)B * H * nsplit * (size_t)(D + 2) * sizeof(float);
-    LLM_REQUIRE(workspace != nullptr && workspace_bytes >= need,
+  if (!p.direct && !p.wgm) {  // (the workgroup merge keeps its splits' states in LDS)
+    LLM_REQUIRE(workspace != nullptr && workspace_bytes >= p.workspace_bytes,
                 "pa_decode: workspace too small (see pa_decode_workspace_bytes)");
     a.part_acc = static_cast<float*>(workspace);
-    a.part_ml = a.part_acc + (size_t)B * H * nsplit * D;
+    a.part_ml = a.part_acc + (size_t)B * H * p.nsplit * D;
   }
+  const PaTuning tn = pa_tuning();
   a.balance16 = tn.beam_balance16;
   // beam-group workgroups in split-major order (PaSplitArgs::smaj).  Same box,
   // C4 (profiles/r06/c4_smaj_ab.txt): 12,719-12,737 against 12,604-12,617
   // tok/s; the launch's HBM bytes 1.031 -> 1.014x algorithmic
   // (profiles/pmc_attention_c4.json), the exits by dispatch slot unchanged
   a.smaj = a.group == 4 && tn.beam_smaj ? 1 : 0;
-  a.beam4 = use_beam4 ? 1 : 0;
-  a.steal = a.group == 4 ? steal_ctr : nullptr;
-  if (wgm) {
+  a.beam4 = p.beam4 ? 1 : 0;
+  if (p.steal && a.group == 4)  // the caller's counters, or the tuning build's (standalone launches)
+    a.steal = rows && rows->beam_ctr ? rows->beam_ctr
+                                     : tune_steal_counters(2 * (size_t)((B + 3) / 4) * H);
+  if (p.wgm) {
     a.wgm = 1;
-    a.out16 = static_cast<_Float16*>(rows->out16);
-    a.pack = rows->pack;
-    a.out = rows->keep_out || f32_rows ? out : nullptr;
+    a.out16 = rows ? static_cast<_Float16*>(rows->out16) : nullptr;
+    a.pack = rows ? rows->pack : 0;
+    a.out = f32_rows || (rows && rows->keep_out) ? out : nullptr;
     if (oproj) {
-      a.o_acc = rows->o_acc;
-      a.o_x = rows->o_x;
+      a.o_acc = rows->o_acc, a.o_x = rows->o_x, a.o_n = rows->o_n, a.o_flag = rows->o_flag;
       a.wo_heads = static_cast<const _Float16*>(rows->wo_heads);
-      a.o_n = rows->o_n;
-      a.o_flag = rows->o_flag;
     }
   }
-  hipError_t e;
-  bool beam = false;  // the beam kernel ran: every split holds a partial
-  switch (D) {
-    case 32: e = dispatch_kvt<32>(a, kv->kv_dtype, TS, direct, st, &beam); break;
-    case 64: e = dispatch_kvt<64>(a, kv->kv_dtype, TS, direct, st, &beam); break;
-    case 128: e = dispatch_kvt<128>(a, kv->kv_dtype, TS, direct, st, &beam); break;
-    default: e = dispatch_kvt<256>(a, kv->kv_dtype, TS, direct, st, &beam); break;
-  }
+  const hipError_t e =
+      pa_for_shape(D, TS, kv->kv_dtype, hipErrorInvalidValue, [&](auto d, auto ts, auto k) {
+        return launch_split<decltype(d)::value, decltype(ts)::value, decltype(k)::value>(a, p, st);
+      });
   if (e != hipSuccess) return fail(LLM_ERR_HIP, std::string("pa_split launch: ") + hipGetErrorString(e));
-  if (wgm) return LLM_OK;
-  if (row_out && !direct)
+  if (p.wgm) return LLM_OK;
+  // the beam kernel ran (p.beam): every split holds a partial
+  if (row_out && !p.direct)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, rows->keep_out ? out : nullptr, rows,
-                                  context_lens, -1, B, H, D, T, TS, beam ? -1 : pps_fixed, nsplit,
+                                  context_lens, -1, B, H, D, T, TS, p.beam ? -1 : p.pps, p.nsplit,
                                   kv->max_tiles, st, out_scale);
-  if (!direct) {
+  if (!p.direct) {
     const int r = pa_merge_splits_internal(a.part_acc, a.part_ml, out, context_lens, B, H, D, T,
-                                           TS, beam ? -1 : pps_fixed, nsplit, kv->max_tiles, st,
+                                           TS, p.beam ? -1 : p.pps, p.nsplit, kv->max_tiles, st,
                                            out_scale);
     if (r != LLM_OK) return r;
   }
@@ -804,20 +537,21 @@ extern "C" int pa_decode_grouped(const pa_kv_view* kv, const float* q, float* ou
                                  int row_group, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   LLM_REQUIRE(row_group >= 1 && row_group <= 4, "pa_decode_grouped: row_group must be in [1, 4]");
-  return pa_decode_internal(kv, q, H * D, out, beam_ids, context_lens, B, H, D, T, sm_scale,
-                            pages_per_split, workspace, workspace_bytes, as_stream(stream),
-                            nullptr, row_group);
+  return pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split, row_group), q, H * D,
+                            out, beam_ids, context_lens, sm_scale, workspace, workspace_bytes,
+                            as_stream(stream));
 }
 
 extern "C" int pa_decode_plan(const pa_kv_view* kv, int B, int H, int D, int T,
                               int pages_per_split, int row_group, int* nsplit, int* form) {
   LLM_REQUIRE(nsplit && form, "pa_decode_plan: NULL output");
   LLM_REQUIRE(row_group >= 1 && row_group <= 4, "pa_decode_plan: row_group must be in [1, 4]");
-  PaPlan p;
-  const int rc = pa_decode_internal(kv, nullptr, H * D, nullptr, nullptr, nullptr, B, H, D, T, 1.f,
-                                    pages_per_split, nullptr, 0, nullptr, nullptr, row_group, &p);
+  PaLaunch p;
+  const int rc = pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split, row_group),
+                                    nullptr, H * D, nullptr, nullptr, nullptr, 1.f, nullptr, 0,
+                                    nullptr, nullptr, &p);
   *nsplit = p.nsplit;
-  *form = p.form;
+  *form = p.form();
   return rc;
 }
 
@@ -825,6 +559,7 @@ extern "C" int pa_decode(const pa_kv_view* kv, const float* q, float* out,
                          const int32_t* beam_ids, const int32_t* context_lens, int B, int H,
                          int D, int T, float sm_scale, int pages_per_split, void* workspace,
                          size_t workspace_bytes, void* stream) {
-  return pa_decode_internal(kv, q, H * D, out, beam_ids, context_lens, B, H, D, T, sm_scale,
-                            pages_per_split, workspace, workspace_bytes, as_stream(stream));
+  return pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split), q, H * D, out,
+                            beam_ids, context_lens, sm_scale, workspace, workspace_bytes,
+                            as_stream(stream));
 }

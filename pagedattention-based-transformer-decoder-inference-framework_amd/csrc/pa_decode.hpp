@@ -4,11 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include "llm_decoder.h"
+#include "pa_plan.hpp"
 
 namespace llm {
 
-// pa_decode with a row stride for q (the decoder reads q in place from the
-// fused qkv projection output, rows of 3*hid floats).
 // Optional per-row conversions of the attention output fused into the split
 // merge (the o_proj input): int8 + inv_scale (per-row quantisation) and/or fp16.
 struct PaRowOutputs {
@@ -17,10 +16,6 @@ struct PaRowOutputs {
   void* out16 = nullptr;
   int pack = 0;  // q / out16 in packed-A order (common.hpp a_frag_off_*)
   int keep_out = 1;  // 0: a split launch skips the fp32 `out` rows (only q / out16 are read)
-  // 1 (with q and out16 NULL): the consumer quantises the fp32 `out` rows
-  // itself (the INT8 o_proj's quantising prologue), so a split launch may
-  // merge its splits inside the workgroup and write `out` (no merge launch)
-  int f32_rows = 0;
   // FP16 decoder, fused o_proj (workgroup-merge launches only, pa_decode_plan
   // form LLM_PA_FORM_WG_MERGE | LLM_PA_FORM_OPROJ): each (row, head)
   // workgroup multiplies its merged head (rounded to fp16, as the o_proj
@@ -47,21 +42,43 @@ struct PaRowOutputs {
   float out_scale = 1.f;
 };
 
-// The launch a call takes (pa_decode_plan): splits per (row, head) and
-// LLM_PA_FORM_* (| LLM_PA_FORM_BEAM).
-struct PaPlan {
-  int nsplit = 0;
-  int form = 0;
-};
+// Bytes per element of a KV pool type (0: unknown type).
+constexpr int kv_elem_size(int kvt) {
+  return kvt == LLM_F16 || kvt == LLM_BF16 ? 2
+         : kvt == LLM_F32                  ? 4
+         : kvt == LLM_I8 || kvt == LLM_FP8 ? 1
+                                           : 0;
+}
 
-// `out` (fp32) may be NULL when `rows` requests an output and the launch splits.
-// plan != NULL: only report the launch (q / out / workspace are not needed).
-int pa_decode_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
-                       const int32_t* beam_ids, const int32_t* context_lens, int B, int H, int D,
-                       int T, float sm_scale, int pages_per_split, void* workspace,
-                       size_t workspace_bytes, hipStream_t st,
-                       const PaRowOutputs* rows = nullptr, int row_group = 1,
-                       PaPlan* plan = nullptr);
+// The request (pa_plan.hpp) of a launch over a view's pages.
+inline PaRequest pa_request(const pa_kv_view* kv, int B, int H, int D, int T, int pages_per_split,
+                            int row_group = 1, PaOut out = PaOut::F32) {
+  PaRequest rq;
+  rq.B = B, rq.H = H, rq.D = D, rq.T = T;
+  if (kv) rq.TS = kv->page_size, rq.max_tiles = kv->max_tiles, rq.kv_dtype = kv->kv_dtype;
+  rq.pps_fixed = pages_per_split > 0 ? std::min(pages_per_split, kMaxPps) : 0;
+  rq.row_group = row_group;
+  rq.out = out;
+  return rq;
+}
+
+// pa_plan on this device: the resident-wave counts come from occupancy queries
+// of the kernels the launch would run (cached), made only for dynamic splits.
+// A count >= 0 given here replaces its query (tests).  LLM_ERR_UNSUPPORTED as
+// pa_plan, and for a shape no split kernel is built for; sets no error text.
+int pa_plan_device(const PaRequest& rq, PaLaunch* launch, long long resident = -1,
+                   long long beam_resident = -1, long long beam4_resident = -1);
+
+// Runs the launch pa_plan_device gives for rq over kv.  q has a row stride (the
+// decoder reads q in place from the fused qkv projection output, rows of 3*hid
+// floats).  rq.out says what comes back: F32 in `out`, every other kind through
+// the pointers of `rows` (F32_ROWS: `out`, as rows [B][H*D]); `out` may be NULL
+// when rows are asked for and the launch splits.
+// plan != NULL: only report the launch (no pointer but kv's is read).
+int pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const float* q, int q_stride,
+                       float* out, const int32_t* beam_ids, const int32_t* context_lens,
+                       float sm_scale, void* workspace, size_t workspace_bytes, hipStream_t st,
+                       const PaRowOutputs* rows = nullptr, PaLaunch* plan = nullptr);
 int pa_pages_per_split(int B, int H, int T, int TS, int max_tiles);
 // Whether the FP16 decoder fuses its o_proj into the attention's workgroup
 // merge (PaRowOutputs::o_acc); always in the product build.
@@ -99,14 +116,6 @@ size_t pa_prefill_ws_bytes(const pa_kv_view* kv, int p0, int m);
 int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
                         int out_stride, int row, int p0, int m, float sm_scale, void* workspace,
                         size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows = nullptr);
-
-// Bytes per element of a KV pool type (0: unknown type).
-inline int kv_elem_size(int kvt) {
-  return kvt == LLM_F16 || kvt == LLM_BF16 ? 2
-         : kvt == LLM_F32                  ? 4
-         : kvt == LLM_I8 || kvt == LLM_FP8 ? 1
-                                           : 0;
-}
 
 // Bytes from page p to page p + 1 of a view's pools (page_stride 0 = dense).
 inline size_t kv_view_page_stride(const pa_kv_view& v) {

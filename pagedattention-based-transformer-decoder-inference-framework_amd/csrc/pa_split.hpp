@@ -99,8 +99,10 @@ struct PaSplitArgs {
   // BEAM: split-major workgroup order (blockIdx = s * groups * H + group * H +
   // head) instead of ((group * H + head) * nsplit + s).  A CU's 4 resident
   // workgroups (blockIdx b, b + 256, b + 512, b + 768 at C4) are then 4 split
-  // pairs of 4 (group, head)s rather than 4 sequence pairs, and the splits of
-  // one (group, head) share an XCD (blockIdx mod 8) and its L2.
+  // pairs of 4 (group, head)s rather than 4 sequence pairs, and, when the
+  // groups * H = ceil(B / 4) * H workgroups of one split are a multiple of 8
+  // (C4: 128), the splits of one (group, head) share an XCD (blockIdx mod 8)
+  // and its L2; otherwise they spread over the XCDs as before.
   int smaj;  // (the earlier fields keep their kernel-argument offsets)
   // LLM_FP8 pools: the V scale of the layer, multiplied into the normalised
   // output once per (row, head) by whichever kernel writes it (the direct
@@ -108,12 +110,6 @@ struct PaSplitArgs {
   // arrives folded into qscale.  Other element types never read it.
   float out_scale;
 };
-
-constexpr int kWgmMaxSplits = 8;  // one merge batch (pa_merge_row_kernel's kMergeBatch)
-constexpr int kOprojMaxD = 128;   // fused o_proj: two W_o column slices of D fp16 in VGPRs
-
-constexpr int kMaxPps = 128;     // page ids held in two registers per lane
-constexpr int kMaxSplits = 128;  // split weights held in two registers per merge lane
 
 // Split length of a row with `ntiles` live tiles.
 __device__ __forceinline__ int row_pps(int pps_fixed, int nsplit, int ntiles) {
@@ -135,7 +131,7 @@ constexpr int pages_per_stage() {
 // nothing per element.
 template <int KVT>
 constexpr int kv_elem_bytes() {
-  return KVT == LLM_F32 ? 4 : KVT == LLM_I8 || KVT == LLM_FP8 ? 1 : 2;
+  return kv_elem_size(KVT);
 }
 
 // Element e of a lane's 16-byte KV piece as fp32.
@@ -173,6 +169,29 @@ constexpr bool kv_shape_ok(int D, int TS, int es) {
 // (scripts/tune_attention.py, variants 0 vs 1).
 constexpr int kKvLoadAux = 2;
 
+// The forms of pa_split_kernel<D, TS, C>: the fields a form changes from these
+// defaults (the plain split kernel of fp16 pages) name it, e.g.
+// PaSplitCfg{.chunk_bytes = 8192, .stages = 1, .min_waves = 8}.  The shipped
+// forms are the pa_cfg_* functions below the kernel.  The notes that follow
+// use the fields' names in capitals.
+struct PaSplitCfg {
+  bool direct = false;      // one split: the wave writes the final output
+  int chunk_bytes = 16384;  // K + V bytes in flight per wave per register stage
+  int aux = kKvLoadAux;     // cache policy of the KV loads
+  int stages = 2;
+  int min_waves = 0;
+  bool load_only = false;  // tuning: the same stream with a trivial consumer
+  bool beam = false;
+  int kvt = LLM_F16;       // element type of the pools
+  bool fullpath = true;    // full pages skip the per-token validity selects
+  bool wgm = false;
+  bool oproj = false;
+  int ring = 0;            // tuning (BEAM): shared chunks through an LDS-DMA ring of `ring` chunks
+  bool stamps = false;     // tuning: per-wave timestamps (PaSplitArgs::stamps)
+  bool interleave = false;
+  bool prio = false;
+};
+
 // STAGES = register stages in flight per wave (2: the next chunk loads while
 // the current one is computed; 1: latency hidden by occupancy alone).
 // MIN_WAVES > 0 asks the compiler for that many waves per SIMD.
@@ -200,37 +219,34 @@ constexpr int kKvLoadAux = 2;
 // long before the last (C4 stamps: exits 34 / 39 / 45 / 52 us by dispatch
 // slot), and the last runs alone with 16 KiB in flight.  Priority outranks age
 // (MI355X_MICROARCH.md, two waves per SIMD, item 4): the laggards catch up.
-template <int D, int TS, bool DIRECT, int CHUNK_BYTES = 16384, int AUX = kKvLoadAux,
-          int STAGES = 2, int MIN_WAVES = 0, bool LOAD_ONLY = false, bool BEAM = false,
-          int KVT = LLM_F16, bool FULLPATH = true, bool WGM = false, bool OPROJ = false,
-          int RING = 0, bool STAMPS = false, bool INTERLEAVE = false, bool PRIO = false>
-__global__ __launch_bounds__(WGM ? 64 * kWgmMaxSplits : 256)
-__attribute__((amdgpu_waves_per_eu(MIN_WAVES > 0 ? MIN_WAVES : 1)))
+template <int D, int TS, PaSplitCfg C>
+__global__ __launch_bounds__(C.wgm ? 64 * kWgmMaxSplits : 256)
+__attribute__((amdgpu_waves_per_eu(C.min_waves > 0 ? C.min_waves : 1)))
 void pa_split_kernel(PaSplitArgs a) {
-  constexpr int ES = kv_elem_bytes<KVT>();
+  constexpr int ES = kv_elem_bytes<C.kvt>();
   constexpr int EPL = 16 / ES;  // elements per lane per 16-byte load
   constexpr int LPT = D / EPL;
   constexpr int TPI = 64 / LPT;
   constexpr int NI = TS / TPI;
   constexpr int PAGE_BYTES = TS * D * ES;
-  constexpr int U = pages_per_stage<PAGE_BYTES, CHUNK_BYTES>();
+  constexpr int U = pages_per_stage<PAGE_BYTES, C.chunk_bytes>();
   constexpr int NR = U * NI;
   static_assert(LPT >= 1 && LPT <= 64 && TS % TPI == 0 && NI >= 1, "bad D/TS");
 
-  static_assert(!(WGM && (DIRECT || BEAM)), "the workgroup merge is a split form");
-  static_assert(!INTERLEAVE || BEAM, "interleaved splits are a beam-group form");
-  constexpr bool IL = BEAM && INTERLEAVE;
-  static_assert(!OPROJ || (WGM && KVT == LLM_F16), "the fused o_proj is a workgroup-merge form");
-  const unsigned long long t_entry = STAMPS ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  if constexpr (BEAM && PRIO) __builtin_amdgcn_s_setprio(3);
+  static_assert(!(C.wgm && (C.direct || C.beam)), "the workgroup merge is a split form");
+  static_assert(!C.interleave || C.beam, "interleaved splits are a beam-group form");
+  constexpr bool IL = C.beam && C.interleave;
+  static_assert(!C.oproj || (C.wgm && C.kvt == LLM_F16), "the fused o_proj is a workgroup-merge form");
+  const unsigned long long t_entry = C.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  if constexpr (C.beam && C.prio) __builtin_amdgcn_s_setprio(3);
   const int lane = lane_id();
-  const int wid = blockIdx.x * (WGM ? a.nsplit : 4) + wave_id_uniform();
-  const int G = BEAM ? 4 : WGM ? 1 : a.group;
+  const int wid = blockIdx.x * (C.wgm ? a.nsplit : 4) + wave_id_uniform();
+  const int G = C.beam ? 4 : C.wgm ? 1 : a.group;
   const int gi = wid % G;  // row within the group (fastest: adjacent waves)
   const int rest = wid / G;
-  const int GH = BEAM && a.smaj ? ((a.B + 3) / 4) * a.H : 1;
-  const int s = BEAM && a.smaj ? rest / GH : rest % a.nsplit;
-  const int gh = BEAM && a.smaj ? rest % GH : rest / a.nsplit;
+  const int GH = C.beam && a.smaj ? ((a.B + 3) / 4) * a.H : 1;
+  const int s = C.beam && a.smaj ? rest / GH : rest % a.nsplit;
+  const int gh = C.beam && a.smaj ? rest % GH : rest / a.nsplit;
   const int h = gh % a.H;
   const int b = (gh / a.H) * G + gi;
   // BEAM: the shared path runs only when all 4 rows exist, route to a valid
@@ -245,15 +261,15 @@ void pa_split_kernel(PaSplitArgs a) {
   constexpr int kPfx = 512;
   bool share = false;
   int grow[4] = {0, 0, 0, 0};  // BEAM: the group's page-table rows
-  int idv[BEAM && !IL ? kPfx / 64 : 1];
-  const bool pfx_on = BEAM && !IL && a.balance16 >= 16 && a.pps == 0 && a.nsplit > 1;
+  int idv[C.beam && !IL ? kPfx / 64 : 1];
+  const bool pfx_on = C.beam && !IL && a.balance16 >= 16 && a.pps == 0 && a.nsplit > 1;
   // IL: interleaved splits (dynamic split length, groups that share: 4 rows
   // of equal context; ragged groups keep the plain schedule's contiguous
   // splits); ilp0 / ilp1 = this wave's row's page ids of tiles s + NS lane and
   // s + NS (64 + lane), requested before `share` is known
   bool il = IL && a.pps == 0 && a.nsplit > 1;
   int ilp0 = -1, ilp1 = -1;
-  if constexpr (BEAM) {
+  if constexpr (C.beam) {
     const int g0 = b - gi;
     int Ti[4];
 #pragma unroll
@@ -304,9 +320,9 @@ void pa_split_kernel(PaSplitArgs a) {
   }
   // BEAM: the page ids of the group's 4 rows, tiles [0, pfx_lim), read once
   // by the prefix scan below and reused for this split's page ids
-  __shared__ int pfx_lds[BEAM && !IL ? 4 : 1][BEAM && !IL ? kPfx : 1];
+  __shared__ int pfx_lds[C.beam && !IL ? 4 : 1][C.beam && !IL ? kPfx : 1];
   int pfx_lim = 0;
-  if constexpr (BEAM && !IL) {
+  if constexpr (C.beam && !IL) {
     // Cost-balanced splits: a split's beam-private tiles are loaded by every
     // wave (4x the per-wave bytes of a shared tile, which the workgroup loads
     // once), so equal tile counts leave the splits holding the private tail
@@ -361,16 +377,16 @@ void pa_split_kernel(PaSplitArgs a) {
       nsh_t = min(nsh_t, ntiles);
       if (nsh_t > 0 && nsh_t < ntiles) {
         const long long A = 16, P = a.balance16, ns = a.nsplit;
-        const long long C = A * nsh_t + P * (ntiles - nsh_t);
+        const long long cost = A * nsh_t + P * (ntiles - nsh_t);
         auto start = [&](int k) -> int {  // first tile of split k
           if (k <= 0) return 0;
           if (k >= ns) return ntiles;
-          const long long x = (C * k + ns - 1) / ns;
+          const long long x = (cost * k + ns - 1) / ns;
           if (x <= A * nsh_t) return (int)((x + A - 1) / A);
           return (int)min<long long>(ntiles, nsh_t + (x - A * nsh_t + P - 1) / P);
         };
         // every tile costs >= A, so no split holds more than C/ns/A + 2 tiles
-        if ((C + ns - 1) / ns / A + 2 <= kMaxPps) {
+        if ((cost + ns - 1) / ns / A + 2 <= kMaxPps) {
           tile0 = start(s);
           count = start(s + 1) - tile0;
         }
@@ -381,7 +397,7 @@ void pa_split_kernel(PaSplitArgs a) {
   const int g = lane / LPT;
 
   if (count <= 0) {
-    if constexpr (BEAM && !DIRECT) {
+    if constexpr (C.beam && !C.direct) {
       // the merge of a beam launch reads every split: an empty one holds
       // (m, l, acc) = (sentinel, 0, 0)
       if (lane < LPT) {
@@ -394,14 +410,14 @@ void pa_split_kernel(PaSplitArgs a) {
         a.part_ml[pidx * 2 + 1] = 0.f;
       }
     }
-    if constexpr (DIRECT) {
+    if constexpr (C.direct) {
       if (lane < LPT) {
         float* o = a.out + (size_t)bh * D + c * EPL;
 #pragma unroll
         for (int e = 0; e < EPL; e += 4) *reinterpret_cast<f32x4*>(o + e) = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    if constexpr (!WGM) return;
+    if constexpr (!C.wgm) return;
     count = 0;  // WGM: no partial (the merge reads splits < ns only), but meet the workgroup
   }
 
@@ -411,7 +427,7 @@ void pa_split_kernel(PaSplitArgs a) {
   if (IL && il) {  // requested at entry (r is the group's row gi)
     pid0 = lane < count && ilp0 < a.num_pages ? ilp0 : -1;
     pid1 = 64 + lane < count && ilp1 < a.num_pages ? ilp1 : -1;
-  } else if (BEAM && tile0 + count <= pfx_lim) {  // (r is the group's row gi: read by the prefix scan)
+  } else if (C.beam && tile0 + count <= pfx_lim) {  // (r is the group's row gi: read by the prefix scan)
     if (lane < count) pid0 = pfx_lds[gi][tile0 + lane];
     if (64 + lane < count) pid1 = pfx_lds[gi][tile0 + 64 + lane];
   } else if (r >= 0 && r < a.num_beams) {
@@ -457,15 +473,15 @@ void pa_split_kernel(PaSplitArgs a) {
                                                          ok ? PAGE_BYTES : 0, 0x00020000);
 #pragma unroll
       for (int i = 0; i < NI; ++i)
-        kk[u * NI + i] = __builtin_amdgcn_raw_buffer_load_b128(krs, lane_off + i * 1024, 0, AUX);
+        kk[u * NI + i] = __builtin_amdgcn_raw_buffer_load_b128(krs, lane_off + i * 1024, 0, C.aux);
 #pragma unroll
       for (int i = 0; i < NI; ++i)
-        vv[u * NI + i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, lane_off + i * 1024, 0, AUX);
+        vv[u * NI + i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, lane_off + i * 1024, 0, C.aux);
     }
   };
 
   auto compute = [&](const u32x4 (&kk)[NR], const u32x4 (&vv)[NR], int p0) {
-    if constexpr (LOAD_ONLY) {  // tuning: the same stream with a trivial consumer
+    if constexpr (C.load_only) {  // tuning: the same stream with a trivial consumer
       uint32_t x = 0;
 #pragma unroll
       for (int i = 0; i < NR; ++i) x ^= kk[i][0] ^ kk[i][3] ^ vv[i][1] ^ vv[i][2];
@@ -484,7 +500,7 @@ void pa_split_kernel(PaSplitArgs a) {
       for (int i = 0; i < NI; ++i) {
         float d = 0.f;
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) d = fmaf(qv[e], kv_at<KVT>(kk[u * NI + i], e), d);
+        for (int e = 0; e < EPL; ++e) d = fmaf(qv[e], kv_at<C.kvt>(kk[u * NI + i], e), d);
         d = group_sum<LPT>(d);
         valid[i] = FULL || (ok && (tok_base + i * TPI) < Tb);
         sc[i] = valid[i] ? d : kNegSentinel;
@@ -503,7 +519,7 @@ void pa_split_kernel(PaSplitArgs a) {
         // NaN/Inf in a never-written page: select them away (0 * NaN = NaN).
         const u32x4 vraw = FULL || valid[i] ? vv[u * NI + i] : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, kv_at<KVT>(vraw, e), acc[e]);
+        for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, kv_at<C.kvt>(vraw, e), acc[e]);
       }
       m = mnew;
     };
@@ -514,7 +530,7 @@ void pa_split_kernel(PaSplitArgs a) {
       const bool ok = (j < count) && (pg >= 0);
       const int tile = tile0 + j * (IL ? tstride : 1);
       const int tok_base = tile * TS + g;
-      if (FULLPATH && ok && (tile + 1) * TS <= Tb)
+      if (C.fullpath && ok && (tile + 1) * TS <= Tb)
         page_math(std::true_type{}, u, ok, tok_base);
       else
         page_math(std::false_type{}, u, ok, tok_base);
@@ -524,16 +540,16 @@ void pa_split_kernel(PaSplitArgs a) {
   const int nchunks = (count + U - 1) / U;
   int ch0 = 0;  // first chunk of the per-wave direct path
   unsigned long long t_load = 0, t_shared = 0;
-  if constexpr (STAMPS) {
+  if constexpr (C.stamps) {
     (void)page_of(0);  // the page ids have arrived
     t_load = __builtin_amdgcn_s_memrealtime();
   }
-  if constexpr (BEAM) {
+  if constexpr (C.beam) {
     static_assert(NR % 2 == 0, "beam prefetch splits a chunk's 2*NR pieces in quarters");
     constexpr int QP = NR / 2;  // pieces per wave per chunk
-    static_assert(RING == 0 || (RING >= 3 && (RING - 2) * QP < 64), "ring of 3+ chunks");
+    static_assert(C.ring == 0 || (C.ring >= 3 && (C.ring - 2) * QP < 64), "ring of 3+ chunks");
     __shared__ int pid_lds[4][128];
-    __shared__ __attribute__((aligned(16))) u32x4 kvbuf[RING > 0 ? RING : 2][2 * NR][64];
+    __shared__ __attribute__((aligned(16))) u32x4 kvbuf[C.ring > 0 ? C.ring : 2][2 * NR][64];
     if (share) {
       pid_lds[gi][lane] = pid0;
       pid_lds[gi][64 + lane] = pid1;
@@ -569,10 +585,10 @@ void pa_split_kernel(PaSplitArgs a) {
           const uint8_t* pool = q < NR ? a.k_pool : a.v_pool;
           const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(pool + off), (short)0,
                                                             ok ? PAGE_BYTES : 0, 0x00020000);
-          qr[t] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off + i * 1024, 0, AUX);
+          qr[t] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off + i * 1024, 0, C.aux);
         }
       };
-      if constexpr (RING > 0) {
+      if constexpr (C.ring > 0) {
         // LDS-DMA ring (tuning): each wave's quarter of chunk cc goes straight
         // from HBM into ring slot cc % RING (buffer_load ... lds: lane-linear,
         // no VGPR stage, no ds_write pass), RING - 1 chunks in flight per
@@ -584,7 +600,7 @@ void pa_split_kernel(PaSplitArgs a) {
         // every wait counts the same number of loads.
         if (nsh > 0) {
           auto dma = [&](int cc) {
-            const int slot = cc % RING;
+            const int slot = cc % C.ring;
 #pragma unroll
             for (int t = 0; t < QP; ++t) {
               const int q = gi * QP + t;
@@ -599,15 +615,15 @@ void pa_split_kernel(PaSplitArgs a) {
                                                                 ok ? PAGE_BYTES : 0, 0x00020000);
               __builtin_amdgcn_raw_ptr_buffer_load_lds(
                   rs, (__attribute__((address_space(3))) void*)&kvbuf[slot][q][0], 16,
-                  lane_off + i * 1024, 0, 0, AUX);
+                  lane_off + i * 1024, 0, 0, C.aux);
             }
           };
 #pragma unroll
-          for (int c0 = 0; c0 < RING - 1; ++c0) dma(c0);
+          for (int c0 = 0; c0 < C.ring - 1; ++c0) dma(c0);
           for (int cc = 0; cc < nsh; ++cc) {
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"((RING - 2) * QP)
+            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"((C.ring - 2) * QP)
                          : "memory");
-            const int cur = cc % RING;
+            const int cur = cc % C.ring;
             u32x4 kk[NR], vv[NR];
             // the slot's reads as one asm block (+ lgkmcnt(0)): read through
             // plain LDS loads, the compiler would retire every DMA in flight
@@ -625,7 +641,7 @@ void pa_split_kernel(PaSplitArgs a) {
                   "=&v"(vv[2]), "=&v"(vv[3])
                 : "v"(ra)
                 : "memory");
-            dma(cc + RING - 1);
+            dma(cc + C.ring - 1);
             compute(kk, vv, cc * U);
           }
           // the zero-record tail loads write LDS the ring no longer reads;
@@ -640,7 +656,7 @@ void pa_split_kernel(PaSplitArgs a) {
         if (nsh > 1) quarter(qr, 1);
         __syncthreads();
         for (int cc = 0; cc < nsh; ++cc) {
-          if constexpr (PRIO) {  // (uniform: nsh and cc are)
+          if constexpr (C.prio) {  // (uniform: nsh and cc are)
             if (cc == nsh / 4) __builtin_amdgcn_s_setprio(2);
             if (cc == nsh / 2) __builtin_amdgcn_s_setprio(1);
             if (cc == (3 * nsh) / 4) __builtin_amdgcn_s_setprio(0);
@@ -668,10 +684,10 @@ void pa_split_kernel(PaSplitArgs a) {
     // workgroup that shares nothing (ragged group, nsh == 0) or whose last
     // quarter of chunks set nothing drops it here, so it never streams its
     // private tiles at top priority past the shared-prefix laggards
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+    if constexpr (C.prio) __builtin_amdgcn_s_setprio(0);
   }
-  if constexpr (STAMPS) t_shared = __builtin_amdgcn_s_memrealtime();
-  if constexpr (STAGES == 1) {
+  if constexpr (C.stamps) t_shared = __builtin_amdgcn_s_memrealtime();
+  if constexpr (C.stages == 1) {
     u32x4 kA[NR], vA[NR];
     for (int ch = ch0; ch < nchunks; ++ch) {
       issue(kA, vA, ch * U);
@@ -706,7 +722,7 @@ void pa_split_kernel(PaSplitArgs a) {
     m = mn;
   }
 
-  if constexpr (WGM) {
+  if constexpr (C.wgm) {
     // The workgroup's waves are the splits of one (b, h): their states meet in
     // LDS and wave 0 merges them with pa_merge_row_kernel's arithmetic (same
     // weights, same sequential order over splits 0..7, zero weights past ns),
@@ -728,10 +744,10 @@ void pa_split_kernel(PaSplitArgs a) {
     // contiguous); the first round's W_o slices are in flight across the merge
     constexpr int KG = D / 8;
     constexpr int CF = KG >= 32 ? 1 : 32 / KG;
-    const int o_n = OPROJ ? a.o_n : 0;
+    const int o_n = C.oproj ? a.o_n : 0;
     const int ocol0 = s * 64 + lane;
     const int ostride = 64 * a.nsplit;
-    f16x8 wcur[OPROJ ? CF : 1][OPROJ ? KG : 1];
+    f16x8 wcur[C.oproj ? CF : 1][C.oproj ? KG : 1];
     auto load_round = [&](int base) {
 #pragma unroll
       for (int j = 0; j < CF; ++j) {
@@ -741,10 +757,10 @@ void pa_split_kernel(PaSplitArgs a) {
         for (int kg = 0; kg < KG; ++kg) wcur[j][kg] = src[(size_t)kg * o_n];
       }
     };
-    if constexpr (OPROJ) load_round(ocol0);
+    if constexpr (C.oproj) load_round(ocol0);
     __syncthreads();
-    if (!OPROJ && s != 0) return;
-    __shared__ __attribute__((aligned(16))) _Float16 wg_o[OPROJ ? D : 8];
+    if (!C.oproj && s != 0) return;
+    __shared__ __attribute__((aligned(16))) _Float16 wg_o[C.oproj ? D : 8];
     if (s == 0) {
       const int pps = row_pps(a.pps, a.nsplit, ntiles);
       const int ns = min(a.nsplit, (ntiles + pps - 1) / pps);
@@ -765,7 +781,7 @@ void pa_split_kernel(PaSplitArgs a) {
             L += ls * ws;
           }
         float inv = 1.0f / (L + 1e-6f);
-        if constexpr (KVT == LLM_FP8) inv *= a.out_scale;  // V's scale, folded as the merge kernels fold it
+        if constexpr (C.kvt == LLM_FP8) inv *= a.out_scale;  // V's scale, folded as the merge kernels fold it
         float am[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; ++e) am[e] = 0.f;
@@ -788,7 +804,7 @@ void pa_split_kernel(PaSplitArgs a) {
           for (int e = 0; e < EPL; e += 4) *reinterpret_cast<f32x4*>(op + e) = f32x4{o[e], o[e + 1], o[e + 2], o[e + 3]};
         }
         if (a.out16) {
-          static_assert(KVT != LLM_F16 || EPL == 8, "fp16 lanes hold 8 dims: one 16-byte store");
+          static_assert(C.kvt != LLM_F16 || EPL == 8, "fp16 lanes hold 8 dims: one 16-byte store");
           if constexpr (EPL == 8) {  // (fp16 pools only: pa_decode_internal's wgm_ok)
             f16x8 pk;
 #pragma unroll
@@ -797,13 +813,13 @@ void pa_split_kernel(PaSplitArgs a) {
                                                         : (size_t)b * hid + k0)) = pk;
           }
         }
-        if constexpr (OPROJ) {
+        if constexpr (C.oproj) {
 #pragma unroll
           for (int e = 0; e < EPL; ++e) wg_o[c * EPL + e] = (_Float16)o[e];
         }
       }
     }  // s == 0
-    if constexpr (OPROJ) {
+    if constexpr (C.oproj) {
       // o_acc[b][n] += sum_k o16[k] W_o[h D + k][n] for this wave's columns:
       // fp16 products, fp32 sums (v_dot2_f32_f16), one returning int64 atomic
       // per column (64 consecutive columns = 512 B per atomic instruction); the
@@ -855,9 +871,9 @@ void pa_split_kernel(PaSplitArgs a) {
   }
 
   if (lane < LPT) {
-    if constexpr (DIRECT) {
+    if constexpr (C.direct) {
       float inv = 1.0f / (l + 1e-6f);
-      if constexpr (KVT == LLM_FP8) inv *= a.out_scale;  // V's scale (1 through the public entries)
+      if constexpr (C.kvt == LLM_FP8) inv *= a.out_scale;  // V's scale (1 through the public entries)
       float* o = a.out + (size_t)bh * D + c * EPL;
 #pragma unroll
       for (int e = 0; e < EPL; e += 4)
@@ -874,7 +890,7 @@ void pa_split_kernel(PaSplitArgs a) {
       }
     }
   }
-  if constexpr (STAMPS) {
+  if constexpr (C.stamps) {
     if (lane == 0) {
       unsigned long long* st = a.stamps + (size_t)wid * 5;
       st[0] = t_entry;
@@ -888,5 +904,92 @@ void pa_split_kernel(PaSplitArgs a) {
     }
   }
 }
+
+// The shipped forms, each named once: the launch (pa_decode.hip launch_split)
+// and every occupancy query that sizes the same launch's splits read the same
+// function, so the two cannot diverge.  kvt is the pools' element type.
+constexpr PaSplitCfg pa_cfg_split(int D, int TS, int kvt, bool direct = false) {
+  return {.direct = direct, .stages = split_stages(D, TS, kv_elem_size(kvt)), .kvt = kvt};
+}
+// Workgroup merge (fp16 pools, and LLM_FP8 pools where fp8_wgm_shape_ok), and
+// with the FP16 decoder's o_proj fused into it (fp16 pools, D <= kOprojMaxD).
+constexpr PaSplitCfg pa_cfg_wgm(int D, int TS, int kvt = LLM_F16) {
+  return {.stages = split_stages(D, TS, kv_elem_size(kvt)), .kvt = kvt, .wgm = true};
+}
+constexpr PaSplitCfg pa_cfg_wgm_fp8(int D, int TS) { return pa_cfg_wgm(D, TS, LLM_FP8); }
+constexpr PaSplitCfg pa_cfg_wgm_oproj(int D, int TS) {
+  return {.stages = split_stages(D, TS, 2), .wgm = true, .oproj = true};
+}
+// Beam groups of 4 fp16 rows: 8 KiB register stages: 112 VGPRs, 4 waves per
+// SIMD.  The 16 KiB form (179 VGPRs, 2 waves) spent 27 % of its wave time in
+// issue stalls and 20 % parked (SQ PMC, scripts/gpu_sq_pmc.sh); same-box A/B
+// of the C4 launch: 72-74 vs 76 us (scripts/ab_attention_lib.py,
+// -DLLM_BEAM_CHUNK=)
+#ifndef LLM_BEAM_CHUNK
+#define LLM_BEAM_CHUNK 8192
+#define LLM_BEAM_WAVES 0
+#endif
+constexpr PaSplitCfg pa_cfg_beam() {
+  return {.chunk_bytes = LLM_BEAM_CHUNK, .min_waves = LLM_BEAM_WAVES, .beam = true,
+          .interleave = true, .prio = true};
+}
+
+// Runtime (D, TS, kvt) to compile-time constants: f(D, TS, KVT as
+// std::integral_constant) for a shape the split kernel is built for (D 32 / 64
+// / 128 / 256, pages of 16 or 32 tokens that pass kv_shape_ok, the five
+// element types), `unsupported` for any other.
+template <class R, class F>
+R pa_for_shape(int D, int TS, int kvt, R unsupported, F&& f) {
+  auto by_ts = [&](auto d, auto k) -> R {
+    constexpr int DD = decltype(d)::value, ES = kv_elem_size(decltype(k)::value);
+    if constexpr (kv_shape_ok(DD, 16, ES))
+      if (TS == 16) return f(d, std::integral_constant<int, 16>{}, k);
+    if constexpr (kv_shape_ok(DD, 32, ES))
+      if (TS == 32) return f(d, std::integral_constant<int, 32>{}, k);
+    return unsupported;
+  };
+  auto by_kvt = [&](auto d) -> R {
+    switch (kvt) {
+      case LLM_F16: return by_ts(d, std::integral_constant<int, LLM_F16>{});
+      case LLM_BF16: return by_ts(d, std::integral_constant<int, LLM_BF16>{});
+      case LLM_F32: return by_ts(d, std::integral_constant<int, LLM_F32>{});
+      case LLM_I8: return by_ts(d, std::integral_constant<int, LLM_I8>{});
+      case LLM_FP8: return by_ts(d, std::integral_constant<int, LLM_FP8>{});
+      default: return unsupported;
+    }
+  };
+  switch (D) {
+    case 32: return by_kvt(std::integral_constant<int, 32>{});
+    case 64: return by_kvt(std::integral_constant<int, 64>{});
+    case 128: return by_kvt(std::integral_constant<int, 128>{});
+    case 256: return by_kvt(std::integral_constant<int, 256>{});
+    default: return unsupported;
+  }
+}
+
+// The tuning build's hooks into the launch (csrc/tune/pa_decode_tune.hip; the
+// switches are pa_tuning.hpp's).
+#if LLM_TUNING
+// An experiment form of a beam-group split launch (pa_beam4_kernel, the steal
+// form, the MFMA beam kernel, the loads-only / stamped / LDS-DMA ring variants
+// of the shipped form) when its switch is on: launches it, *e = its status,
+// returns true.  false: the shipped form runs.
+bool tune_launch_form(const PaSplitArgs& a, int D, int TS, dim3 grid, hipStream_t st,
+                      hipError_t* e);
+long long tune_beam4_resident_for(int D, int TS);
+// the MFMA beam kernel's occupancy when LLM_BEAM_MFMA=1 (true; *e its status)
+bool tune_beam_occupancy(int D, int TS, int* blocks, hipError_t* e);
+// counters of standalone steal launches (no decoder-owned ones; launches must
+// not overlap), nullptr unless LLM_BEAM_STEAL=1
+unsigned* tune_steal_counters(size_t n);
+#else
+inline bool tune_launch_form(const PaSplitArgs&, int, int, dim3, hipStream_t, hipError_t*) {
+  return false;
+}
+constexpr long long tune_beam4_resident_for(int, int) { return 0; }
+inline bool tune_beam_occupancy(int, int, int*, hipError_t*) { return false; }
+inline unsigned* tune_steal_counters(size_t) { return nullptr; }
+#endif
+
 
 }  // namespace llm

@@ -2,15 +2,13 @@
 // The product library is compiled against the constant defaults below: every
 // switch folds away.  The tuning build (make tune, -DLLM_TUNING=1) reads them
 // from the environment per launch and may route a beam-group launch to one of
-// the experiment kernels (csrc/tune/pa_decode_tune.hip); nothing else in the
-// product sources depends on LLM_TUNING for attention.
+// the experiment kernels (csrc/tune/pa_decode_tune.hip, through the hooks at
+// the end of pa_split.hpp); nothing else in the product sources depends on
+// LLM_TUNING for attention.  No HIP types here: the planner (pa_plan.hpp) reads
+// the table on the host.
 #pragma once
 
-#include "common.hpp"
-
 namespace llm {
-
-struct PaSplitArgs;
 
 struct PaTuning {
   bool wg_merge = true;        // LLM_WG_MERGE=0: split + merge launches, no workgroup merge
@@ -35,26 +33,8 @@ constexpr bool steal_shape_ok(int D, int TS) {
 
 #if LLM_TUNING
 PaTuning pa_tuning();
-// An experiment form of a beam-group split launch (pa_beam4_kernel, the steal
-// form, the MFMA beam kernel, the loads-only / stamped / LDS-DMA ring variants
-// of the shipped form) when its switch is on: launches it, *e = its status,
-// returns true.  false: the shipped form runs.
-bool tune_launch_form(const PaSplitArgs& a, int D, int TS, dim3 grid, hipStream_t st,
-                      hipError_t* e);
-long long tune_beam4_resident_for(int D, int TS);
-// the MFMA beam kernel's occupancy when LLM_BEAM_MFMA=1 (true; *e its status)
-bool tune_beam_occupancy(int D, int TS, int* blocks, hipError_t* e);
-// counters of standalone steal launches (no decoder-owned ones; launches must
-// not overlap), nullptr unless LLM_BEAM_STEAL=1
-unsigned* tune_steal_counters(size_t n);
 #else
 constexpr PaTuning pa_tuning() { return PaTuning{}; }
-inline bool tune_launch_form(const PaSplitArgs&, int, int, dim3, hipStream_t, hipError_t*) {
-  return false;
-}
-constexpr long long tune_beam4_resident_for(int, int) { return 0; }
-inline bool tune_beam_occupancy(int, int, int*, hipError_t*) { return false; }
-inline unsigned* tune_steal_counters(size_t) { return nullptr; }
 #endif
 
 }  // namespace llm

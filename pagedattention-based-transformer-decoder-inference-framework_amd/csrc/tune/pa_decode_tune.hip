@@ -1,11 +1,12 @@
 // Tuning build only (make tune -> libllm_decoder_hip_tune.so; never in
 // libllm_decoder_hip.so): the beam-group attention experiments that measured
 // slower than the shipped BEAM form of pa_split_kernel, the
-// tuning table pa_decode.hip reads (pa_tuning.hpp: the switches from the
-// environment, and tune_launch_form, which routes a beam-group launch to the
-// experiment switched on), and the pa_decode_tune A/B entry of the split
-// kernel's register-stage / cache-policy variants (scripts/bench_kernels.py,
-// scripts/tune_attention.py).
+// tuning table the planner and pa_decode.hip read (pa_tuning.hpp: the switches
+// from the environment; the hooks at the end of pa_split.hpp: tune_launch_form
+// routes a beam-group launch to the experiment switched on), the pa_decode_tune
+// A/B entry of the split kernel's register-stage / cache-policy variants
+// (scripts/bench_kernels.py, scripts/tune_attention.py; each variant is the
+// PaSplitCfg fields it changes) and pa_plan_tune, the planner's test entry.
 #include "tune/pa_decode_tune.hpp"
 #include "tune/pa_beam_steal.hpp"
 #include "pa_tuning.hpp"
@@ -750,12 +751,10 @@ hipError_t tune_launch_beam_mfma(const PaSplitArgs& a, dim3 grid, hipStream_t st
 }
 
 hipError_t tune_launch_beam_loads_only(const PaSplitArgs& a, dim3 grid, hipStream_t st) {
-#ifndef LLM_BEAM_CHUNK
-#define LLM_BEAM_CHUNK 8192
-#define LLM_BEAM_WAVES 0
-#endif
-  hipLaunchKernelGGL((pa_split_kernel<128, 16, false, LLM_BEAM_CHUNK, kKvLoadAux, 2, LLM_BEAM_WAVES,
-                                      true, true>), grid, dim3(256), 0, st, a);
+  // (the cost-balanced contiguous splits, as kBeamContiguous below)
+  constexpr PaSplitCfg kLoadsOnly{.chunk_bytes = LLM_BEAM_CHUNK, .min_waves = LLM_BEAM_WAVES,
+                                  .load_only = true, .beam = true};
+  hipLaunchKernelGGL((pa_split_kernel<128, 16, kLoadsOnly>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -767,9 +766,9 @@ hipError_t tune_launch_beam_ring(const PaSplitArgs& a, dim3 grid, hipStream_t st
   auto go = [&](auto r, auto lo) {
     constexpr int R = decltype(r)::value;
     constexpr bool LO = decltype(lo)::value;
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, LO, true, LLM_F16,
-                                        true, false, false, R, false, true, true>),
-                       grid, dim3(256), 0, st, a);
+    constexpr PaSplitCfg kRing{.chunk_bytes = 8192, .load_only = LO, .beam = true, .ring = R,
+                               .interleave = true, .prio = true};
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kRing>), grid, dim3(256), 0, st, a);
   };
   auto by_ring = [&](auto lo) {
     switch (ring) {
@@ -805,19 +804,16 @@ hipError_t tune_launch_beam_stamps(const PaSplitArgs& a0, dim3 grid, hipStream_t
   PaSplitArgs a = a0;
   a.stamps = g_stamps;
   g_stamps_waves = waves;
+  constexpr PaSplitCfg kStamped{.chunk_bytes = 8192, .beam = true, .stamps = true};
+  constexpr PaSplitCfg kStampedIl{.chunk_bytes = 8192, .beam = true, .stamps = true, .interleave = true};
+  constexpr PaSplitCfg kStampedIlPrio{.chunk_bytes = 8192, .beam = true, .stamps = true,
+                                      .interleave = true, .prio = true};
   if (env_int("LLM_BEAM_INTERLEAVE", 1) == 0)
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, false, true, LLM_F16,
-                                        true, false, false, 0, true>),
-                       grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kStamped>), grid, dim3(256), 0, st, a);
   else if (env_int("LLM_BEAM_PRIO", 1) == 0)
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, false, true, LLM_F16,
-                                        true, false, false, 0, true, true, false>),
-                       grid, dim3(256), 0, st, a);
-
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kStampedIl>), grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, false, true, LLM_F16,
-                                        true, false, false, 0, true, true, true>),
-                       grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kStampedIlPrio>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -952,15 +948,14 @@ bool tune_launch_form(const PaSplitArgs& a, int D, int TS, dim3 grid, hipStream_
     return true;
   }
   if (env_int("LLM_BEAM_PRIO", 1) == 0) {  // interleaved splits without the priority ranking
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, false, true, LLM_F16,
-                                        true, false, false, 0, false, true, false>),
-                       grid, dim3(256), 0, st, a);
+    constexpr PaSplitCfg kBeamNoPrio{.chunk_bytes = 8192, .beam = true, .interleave = true};
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kBeamNoPrio>), grid, dim3(256), 0, st, a);
     *e = hipGetLastError();
     return true;
   }
   if (env_int("LLM_BEAM_INTERLEAVE", 1) == 0) {  // round 4's contiguous cost-balanced splits
-    hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, kKvLoadAux, 2, 0, false, true>),
-                       grid, dim3(256), 0, st, a);
+    constexpr PaSplitCfg kBeamContiguous{.chunk_bytes = 8192, .beam = true};
+    hipLaunchKernelGGL((pa_split_kernel<128, 16, kBeamContiguous>), grid, dim3(256), 0, st, a);
     *e = hipGetLastError();
     return true;
   }
@@ -996,6 +991,40 @@ extern "C" long long pa_tune_stamps(unsigned long long* host, long long max_wave
   return (long long)n;
 }
 
+// Tuning hook: the launch planner (pa_plan.hpp) for explicit request fields,
+// so tests reach the row kinds the product ABI cannot ask for.  out_kind is a
+// PaOut value, rows16 its OPROJ flag; a resident count < 0 is queried from the
+// device, any other is taken as given.  The request passes pa_decode_internal's
+// own checks first (over a view of these fields with placeholder pointers,
+// which a plan-only call never reads).
+extern "C" int pa_plan_tune(int B, int H, int D, int T, int page_size, int max_tiles, int kv_dtype,
+                            int pages_per_split, int row_group, int out_kind, int rows16,
+                            long long resident, long long beam_resident, long long beam4_resident,
+                            int* nsplit, int* form) {
+  LLM_REQUIRE(nsplit && form, "pa_plan_tune: NULL output");
+  LLM_REQUIRE(out_kind >= 0 && out_kind <= (int)PaOut::OPROJ, "pa_plan_tune: out_kind");
+  *nsplit = *form = 0;
+  static const int32_t placeholder = 0;
+  pa_kv_view kv{};
+  kv.k_pool = kv.v_pool = &placeholder;
+  kv.page_table = &placeholder;
+  kv.num_pages = 1 << 20;
+  kv.num_beams = std::max(B, 1);
+  kv.num_heads = H, kv.head_dim = D, kv.page_size = page_size, kv.max_tiles = max_tiles;
+  kv.kv_dtype = kv_dtype;
+  PaRequest rq = pa_request(&kv, B, H, D, T, pages_per_split, row_group, (PaOut)out_kind);
+  rq.rows16 = rows16 != 0;
+  PaLaunch p;
+  const int rc = pa_decode_internal(&kv, rq, nullptr, H * D, nullptr, nullptr, nullptr, 1.f,
+                                    nullptr, 0, nullptr, nullptr, &p);
+  if (rc != LLM_OK) return rc;
+  if (pa_plan_device(rq, &p, resident, beam_resident, beam4_resident) != LLM_OK)
+    return fail(LLM_ERR_UNSUPPORTED, "pa_plan_tune: more splits than a row may have");
+  *nsplit = p.nsplit;
+  *form = p.form();
+  return LLM_OK;
+}
+
 // Tuning hook (not part of include/llm_decoder.h): run the split kernel of
 // D=128 / TS=16 in a given variant so scripts/bench_kernels.py can compare
 // register-stage sizes and cache policies in one process.
@@ -1028,38 +1057,38 @@ extern "C" int pa_decode_tune(int variant, const pa_kv_view* kv, const float* q,
   hipStream_t st = as_stream(stream);
   const dim3 grid((B * H * nsplit + 3) / 4), block(256);
   switch (variant) {  // NOLINT
-    case 0: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 0>), grid, block, 0, st, a); break;
-    case 1: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 2>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 0>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 2>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 32768, 0>), grid, block, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 32768, 2>), grid, block, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 2, 1, 8>), grid, block, 0, st, a); break;
-    case 7: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 2, 1, 4>), grid, block, 0, st, a); break;
-    case 8: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 2, 2, 4>), grid, block, 0, st, a); break;
-    case 9: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 2, 1, 6>), grid, block, 0, st, a); break;
-    case 10: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 2, 2, 0, true>), grid, block, 0, st, a); break;
-    case 11: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 8192, 2, 1, 8, true>), grid, block, 0, st, a); break;
-    case 12: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 32768, 2, 2, 0, true>), grid, block, 0, st, a); break;
+    case 0: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 0}>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{}>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192, .aux = 0}>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192}>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 32768, .aux = 0}>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 32768}>), grid, block, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192, .stages = 1, .min_waves = 8}>), grid, block, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.stages = 1, .min_waves = 4}>), grid, block, 0, st, a); break;
+    case 8: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192, .min_waves = 4}>), grid, block, 0, st, a); break;
+    case 9: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192, .stages = 1, .min_waves = 6}>), grid, block, 0, st, a); break;
+    case 10: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.load_only = true}>), grid, block, 0, st, a); break;
+    case 11: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 8192, .stages = 1, .min_waves = 8, .load_only = true}>), grid, block, 0, st, a); break;
+    case 12: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.chunk_bytes = 32768, .load_only = true}>), grid, block, 0, st, a); break;
     // 13: variant 1 without the full-page fast path (every token takes the validity selects)
-    case 13: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 2, 2, 0, false, false, LLM_F16, false>), grid, block, 0, st, a); break;
+    case 13: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.fullpath = false}>), grid, block, 0, st, a); break;
     // 14-18: variant 1 with other cache-policy bits of the KV loads (gfx940-family
     // CPol: sc0 = 1, nt = 2, sc1 = 16): 14 sc0|nt, 15 sc1|nt, 16 sc0|sc1|nt,
     // 17 sc1, 18 sc0; 19: loads only with sc1|nt
-    case 14: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 3>), grid, block, 0, st, a); break;
-    case 15: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 18>), grid, block, 0, st, a); break;
-    case 16: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 19>), grid, block, 0, st, a); break;
-    case 17: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 16>), grid, block, 0, st, a); break;
-    case 18: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 1>), grid, block, 0, st, a); break;
-    case 19: hipLaunchKernelGGL((pa_split_kernel<128, 16, false, 16384, 18, 2, 0, true>), grid, block, 0, st, a); break;
+    case 14: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 3}>), grid, block, 0, st, a); break;
+    case 15: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 18}>), grid, block, 0, st, a); break;
+    case 16: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 19}>), grid, block, 0, st, a); break;
+    case 17: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 16}>), grid, block, 0, st, a); break;
+    case 18: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 1}>), grid, block, 0, st, a); break;
+    case 19: hipLaunchKernelGGL((pa_split_kernel<128, 16, PaSplitCfg{.aux = 18, .load_only = true}>), grid, block, 0, st, a); break;
     // D = 64 (C2): 20 production, 21 one 16 KiB stage, 22 8 KiB stages, 23 one
     // 32 KiB stage, 24 / 25 loads only (16 KiB x 2, 32 KiB x 1)
-    case 20: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 16384, 2, 2>), grid, block, 0, st, a); break;
-    case 21: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 16384, 2, 1>), grid, block, 0, st, a); break;
-    case 22: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 8192, 2, 2>), grid, block, 0, st, a); break;
-    case 23: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 32768, 2, 1>), grid, block, 0, st, a); break;
-    case 24: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 16384, 2, 2, 0, true>), grid, block, 0, st, a); break;
-    case 25: hipLaunchKernelGGL((pa_split_kernel<64, 16, false, 32768, 2, 1, 0, true>), grid, block, 0, st, a); break;
+    case 20: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{}>), grid, block, 0, st, a); break;
+    case 21: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{.stages = 1}>), grid, block, 0, st, a); break;
+    case 22: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{.chunk_bytes = 8192}>), grid, block, 0, st, a); break;
+    case 23: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{.chunk_bytes = 32768, .stages = 1}>), grid, block, 0, st, a); break;
+    case 24: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{.load_only = true}>), grid, block, 0, st, a); break;
+    case 25: hipLaunchKernelGGL((pa_split_kernel<64, 16, PaSplitCfg{.chunk_bytes = 32768, .stages = 1, .load_only = true}>), grid, block, 0, st, a); break;
     default: return fail(LLM_ERR_INVALID, "pa_decode_tune: variant");
   }
   LLM_HIP_RET(hipGetLastError());

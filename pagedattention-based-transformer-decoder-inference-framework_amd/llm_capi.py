@@ -67,6 +67,8 @@ _SIGS = {
     "pa_decode_pages_per_split": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pa_decode_plan": (c_int, [ctypes.POINTER(PaKvView), c_int, c_int, c_int, c_int, c_int, c_int,
                                c_i32p, c_i32p]),
+    # tuning library only: the launch planner on explicit request fields
+    "pa_plan_tune": (c_int, [c_int] * 11 + [c_ll] * 3 + [c_i32p, c_i32p]),
     "pa_decode": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_void_p,
                           c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
                           c_void_p]),
