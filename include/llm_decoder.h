@@ -272,6 +272,25 @@ int argmax_rows(const float* logits, int rows, int V, int32_t* out, void* stream
  * V <= 65536. */
 int sample_rows(const float* logits, int rows, int V, float temperature, int top_k, float top_p,
                 uint64_t seed, int counter, int32_t* out, void* stream);
+/* Beam candidates of one decode step (csrc/beam_select.hip).  logits fp32
+ * [rows][V] device with rows = num_seqs * W, row = seq * W + beam, 1 <= W <= 4;
+ * score_in fp32 [rows] device, a beam's cumulative log-probability, -inf for
+ * a beam that is not live (its row is not read and competes with -inf).
+ * Row stage, one workgroup per row: m = max x, s = sum exp(x - m), and the
+ * row's 2W largest RAW logits (ties: lower token id first), so with W = 1 the
+ * winner is argmax_rows' id whatever the rounding of a log-probability.
+ * Merge stage, one wave per sequence: the W * 2W candidates get
+ *   score = score_in[row] + ((x - m) - log(s + 1e-6))    (sample_rows' sum + 1e-6)
+ * and are ranked by (score descending, parent ascending, token ascending);
+ * the best 2W, in that order, go to cand_score / cand_parent (the beam, 0 ..
+ * W-1) / cand_token, each [num_seqs][2W] device.  Two launches, no atomics,
+ * the same result on every run.  2W <= V <= 65536 (else LLM_ERR_INVALID, as W
+ * outside 1..4: all checked on the host before any launch).  The row stage's
+ * results pass through a scratch buffer the library keeps and grows on demand
+ * (the only part of a call that cannot be captured into a graph: call once
+ * at the largest num_seqs first); calls on different streams must not overlap. */
+int beam_select_rows(const float* logits, const float* score_in, int num_seqs, int W, int V,
+                     float* cand_score, int32_t* cand_parent, int32_t* cand_token, void* stream);
 /* The uniform draw sample_rows uses for (seed, row, counter): splitmix64 of
  * seed ^ (row << 32) ^ counter, top 24 bits / 2^24. */
 float sample_uniform_host(uint64_t seed, int row, int counter);
@@ -307,6 +326,8 @@ void kv_cache_destroy(kv_cache* c);
 int kv_cache_view(const kv_cache* c, int layer, pa_kv_view* out);
 long long kv_cache_num_pages(const kv_cache* c);
 long long kv_cache_free_pages(const kv_cache* c);
+/* Pages copied on write since kv_cache_create (a running count, for measurements). */
+long long kv_cache_cow_copies(const kv_cache* c);
 /* PageTable::assign (page_table.cpp:49-53) / lookup / remove (:64-66), host mirror. */
 int kv_cache_assign(kv_cache* c, int layer, int beam, int head, int tile, int page);
 int kv_cache_lookup(const kv_cache* c, int layer, int beam, int head, int tile);
@@ -335,11 +356,25 @@ int kv_cache_reserve(kv_cache* c, int beam, int n_tokens);
 /* Beam fork: dst's page-table rows := src's (all layers, heads), shared pages
  * refcounted; pages of dst are copied-on-write by kv_cache_append/write. */
 int kv_cache_fork(kv_cache* c, int src_beam, int dst_beam);
+/* Beam re-parenting after a beam-search step: row first_beam + i := what row
+ * first_beam + parent[i] held BEFORE the call (parent[i] in [0, n), host array),
+ * for the tiles covering tokens [0, n_tokens), all layers and heads.  Shared
+ * pages are refcounted as by kv_cache_fork (the next append copies on write);
+ * the pages of a row no child names are released.  A row that names itself
+ * gets no table writes; every entry is read before any entry of its tile is
+ * written, so a permutation (e.g. a swap) is safe.  Only tiles below
+ * ceil(n_tokens / page_size) are walked and equal entries are skipped, where
+ * kv_cache_fork walks all max_tiles: cheap enough to run once per step.
+ * Tiles past n_tokens are left as they are. */
+int kv_cache_reorder(kv_cache* c, int first_beam, int n, const int32_t* parent, int n_tokens);
 /* Release every page of `beam` (refcount-aware). */
 int kv_cache_release(kv_cache* c, int beam);
 /* PageTable::clear (page_table.cpp:39-44): all entries -1, all pages free. */
 int kv_cache_clear(kv_cache* c);
-/* PageTable::sync_to_gpu (page_table.cpp:59-62): push dirty host entries. */
+/* PageTable::sync_to_gpu (page_table.cpp:59-62): push dirty host entries.
+ * Pending copy-on-write page copies go first: two or more of them in ONE
+ * launch (one workgroup per page pair, the pairs staged through pinned
+ * memory), a single one as a device memcpy. */
 int kv_cache_sync(kv_cache* c, void* stream);
 /* Copy n tokens of K and V (host, [n][H][D] in the cache's kv_dtype) for
  * `beam` starting at token position pos into the pools of `layer`. */
@@ -466,6 +501,53 @@ int llm_quantize_weights(const char* fp32_dir, const char* int8_dir, int num_lay
 int llm_decoder_generate(llm_decoder* d, const int32_t* prompts, const int32_t* prompt_lens,
                          int prompt_stride, int batch, int max_gen_len, float temperature,
                          int32_t* out);
+
+/* Beam search over shared prompts (what the reference's stream_chat_beam,
+ * api/router.py, and enable_beam_search stand for: they call greedy generate
+ * beam_width times and get one text beam_width times).  num_seqs prompts, W =
+ * beam_width beams each, rows seq * W + beam; num_seqs * W <= max_batch.
+ * Set-up: prompt[:-1] is prefilled into beam 0's row and forked to the other
+ * beams (shared pages, kv_cache_fork); scores start {0, -inf, ...}.
+ * Each step: the step graph in beam mode (the LM head, then beam_select_rows'
+ * two launches in place of argmax / sampling), the 2W candidates per sequence
+ * copied to the host, the bookkeeping below, kv_cache_reorder per sequence (the
+ * next step's append copies the shared tail page on write), new scores and
+ * tokens uploaded.
+ * Bookkeeping, per sequence, candidates walked in rank order: a candidate whose
+ * token is eos_token joins the finished set if its rank is < W and is ignored
+ * otherwise; any other candidate becomes the next live beam (slot = order of
+ * appearance) until W are live.  A sequence with >= W finished hypotheses is
+ * done: it keeps stepping the same way but records nothing more, and its live
+ * beams are not results.  The search ends when every sequence is done or after
+ * max_new_tokens steps; the live beams of a sequence that is not done then
+ * join its finished set (in beam order) as unterminated hypotheses.  Final
+ * score = sum_logprob / len^length_penalty (len = generated tokens, EOS
+ * included; computed in double, stored as float); the best W by final score
+ * (equal scores: the earlier entry) are returned best first.
+ * out_ids [num_seqs][W][max_new_tokens] (padded with -1), out_len / out_sum_logprob /
+ * out_score [num_seqs][W].  Traces (any may be NULL) hold, per step, the device's
+ * candidates, the live beams chosen (parent slot and token) and the step's logits.
+ * Afterwards the W rows of every sequence stay active (the last live beams,
+ * row_group = W), so llm_decoder_context_len / attention_plan / kv apply.
+ * Both weight types, fp16 and LLM_FP8 pools; vocab_size in [2W, 65536].
+ * A set sampling mode is suspended as in llm_decoder_generate; LLM_ERR_RANGE
+ * as there (results complete). */
+typedef struct llm_beam_options {
+  int beam_width;        /* 1..4 */
+  int max_new_tokens;    /* >= 1 */
+  int eos_token;         /* -1: none */
+  float length_penalty;  /* alpha >= 0; final score = sum_logprob / len^alpha, len = generated tokens incl. EOS */
+  /* optional traces, host unless noted; NULL = off */
+  int32_t* trace_cand_parent; int32_t* trace_cand_token; float* trace_cand_score; /* [steps][num_seqs][2W] */
+  int32_t* trace_live_parent; int32_t* trace_live_token;                          /* [steps][num_seqs][W]  */
+  float* trace_logits_dev;                                                         /* device [steps][rows][V] */
+  int* steps_run;
+} llm_beam_options;
+
+int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts, const int32_t* prompt_lens,
+                            int prompt_stride, int num_seqs, const llm_beam_options* opt,
+                            int32_t* out_ids, int32_t* out_len, float* out_sum_logprob,
+                            float* out_score);
 
 /* Chunked prefill (the is_prefill pass of AttentionCUDA::forward,
  * attention/attention_cuda.hpp:21): append the n tokens (host ids) of active

@@ -15,7 +15,10 @@
 // Both decoders take a keyword kv_dtype ("float16" by default; "fp8" /
 // "float8_e4m3fn": LLM_FP8 KV pages with per-layer scales, set_kv_scales) and
 // have a read-only prefill_kernel ("mfma" / "decode": llm_decoder_prefill_kernel).
-// Additions: generate_batch, set_weights (host numpy arrays), low-level
+// Additions: generate_batch, beam_search / beam_search_batch
+// (llm_decoder_beam_search: [(ids, score), ...] per prompt, best first; what
+// api/router.py's stream_chat_beam loops greedy generate for), the module-level
+// beam_select (beam_select_rows), set_weights (host numpy arrays), low-level
 // begin_synthetic / step for the bench, PageTable / KVTileCache classes with
 // the kv_cache/ API names (page_table.hpp:5-37, kv_tile_cache.hpp:9-41) and
 // paged_attention() over raw device pointers.
@@ -173,6 +176,92 @@ class Decoder {
       return py::none();
     }
     return py::cast(res);
+  }
+
+  // llm_decoder_beam_search over a batch of prompts: per prompt the beam_width
+  // hypotheses [(ids, score), ...], best first (ids: the generated tokens, EOS
+  // included).  return_trace: (results, trace) with trace a dict of numpy
+  // arrays -- cand_parent / cand_token / cand_score [steps][num_seqs][2W],
+  // live_parent / live_token [steps][num_seqs][W], sum_logprob / length
+  // [num_seqs][W], steps -- and, when trace_logits_ptr names a device buffer of
+  // [max_new_tokens][num_seqs * W][V] floats, every step's logits there.
+  py::object beam_search_batch(const std::vector<std::vector<int>>& prompts, int beam_width,
+                               int max_new_tokens, int eos_token_id, float length_penalty,
+                               bool return_trace, uintptr_t trace_logits_ptr) {
+    const int S = (int)prompts.size();
+    if (S == 0) return py::list();
+    if (beam_width < 1 || beam_width > 4)
+      throw std::invalid_argument("beam_search: beam_width must be in [1, 4]");
+    if (max_new_tokens < 1) throw std::invalid_argument("beam_search: max_new_tokens must be >= 1");
+    const int W = beam_width, K = 2 * W;
+    size_t stride = 1;
+    for (auto& p : prompts) stride = std::max(stride, p.size());
+    std::vector<int32_t> flat((size_t)S * stride, 0), lens(S);
+    for (int s = 0; s < S; ++s) {
+      lens[s] = (int32_t)prompts[s].size();
+      std::copy(prompts[s].begin(), prompts[s].end(), flat.begin() + (size_t)s * stride);
+    }
+    const size_t T = (size_t)max_new_tokens;
+    std::vector<int32_t> ids((size_t)S * W * T), len((size_t)S * W);
+    std::vector<float> sum((size_t)S * W), score((size_t)S * W);
+    std::vector<int32_t> cp, ct, lp, lt;
+    std::vector<float> cs;
+    int steps = 0;
+    llm_beam_options o{};
+    o.beam_width = W; o.max_new_tokens = max_new_tokens; o.eos_token = eos_token_id;
+    o.length_penalty = length_penalty;
+    o.steps_run = &steps;
+    if (return_trace) {
+      cp.assign(T * S * K, -1); ct.assign(T * S * K, -1); cs.assign(T * S * K, 0.f);
+      lp.assign(T * S * W, -1); lt.assign(T * S * W, -1);
+      o.trace_cand_parent = cp.data(); o.trace_cand_token = ct.data();
+      o.trace_cand_score = cs.data();
+      o.trace_live_parent = lp.data(); o.trace_live_token = lt.data();
+      o.trace_logits_dev = reinterpret_cast<float*>(trace_logits_ptr);
+    }
+    {
+      py::gil_scoped_release nogil;
+      check(llm_decoder_beam_search(d_, flat.data(), lens.data(), (int)stride, S, &o, ids.data(),
+                                    len.data(), sum.data(), score.data()));
+    }
+    py::list res;
+    for (int s = 0; s < S; ++s) {
+      py::list hyps;
+      for (int w = 0; w < W; ++w) {
+        const int32_t* p = ids.data() + ((size_t)s * W + w) * T;
+        hyps.append(py::make_tuple(std::vector<int>(p, p + len[s * W + w]), score[s * W + w]));
+      }
+      res.append(hyps);
+    }
+    if (!return_trace) return res;
+    auto a3 = [&](auto& v, int n) {
+      using E = typename std::remove_reference_t<decltype(v)>::value_type;
+      py::array_t<E> a({(py::ssize_t)steps, (py::ssize_t)S, (py::ssize_t)n});
+      std::copy(v.begin(), v.begin() + (size_t)steps * S * n, a.mutable_data());
+      return a;
+    };
+    auto a2 = [&](auto& v) {
+      using E = typename std::remove_reference_t<decltype(v)>::value_type;
+      py::array_t<E> a({(py::ssize_t)S, (py::ssize_t)W});
+      std::copy(v.begin(), v.end(), a.mutable_data());
+      return a;
+    };
+    py::dict tr;
+    tr["cand_parent"] = a3(cp, K); tr["cand_token"] = a3(ct, K); tr["cand_score"] = a3(cs, K);
+    tr["live_parent"] = a3(lp, W); tr["live_token"] = a3(lt, W);
+    tr["sum_logprob"] = a2(sum); tr["length"] = a2(len); tr["score"] = a2(score);
+    tr["steps"] = steps;
+    return py::make_tuple(res, tr);
+  }
+  py::object beam_search(const std::vector<int>& input_ids, int beam_width, int max_new_tokens,
+                         int eos_token_id, float length_penalty, bool return_trace,
+                         uintptr_t trace_logits_ptr) {
+    if (input_ids.empty()) throw std::invalid_argument("beam_search: input_ids must not be empty");
+    py::object r = beam_search_batch({input_ids}, beam_width, max_new_tokens, eos_token_id,
+                                     length_penalty, return_trace, trace_logits_ptr);
+    if (!return_trace) return r.cast<py::list>()[0];
+    py::tuple t = r.cast<py::tuple>();
+    return py::make_tuple(t[0].cast<py::list>()[0], t[1]);
   }
 
   void begin_synthetic(int batch, int context_len, uint64_t seed, bool shuffle) {
@@ -350,6 +439,11 @@ class KVTileCache {
     check(kv_cache_set_eviction(c_, policy == "lru" ? LLM_EVICT_LRU : LLM_EVICT_NONE));
   }
   void fork(int src, int dst) { need(); check(kv_cache_fork(c_, src, dst)); }
+  // kv_cache_reorder: row first_beam + i := what row first_beam + parent[i] held
+  void reorder(int first_beam, const std::vector<int32_t>& parent, int n_tokens) {
+    need();
+    check(kv_cache_reorder(c_, first_beam, (int)parent.size(), parent.data(), n_tokens));
+  }
   void release(int beam) { need(); check(kv_cache_release(c_, beam)); }
   void sync_page_table_to_gpu() { need(); check(kv_cache_sync(c_, nullptr)); check(llm_sync()); }
   // KVTileCache::save_to_file / load_from_file (kv_tile_cache.cpp:105-125):
@@ -471,6 +565,14 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("generate", &Decoder::generate)
         .def("generate_batch", &Decoder::generate_batch, py::arg("input_ids"),
              py::arg("max_gen_len"), py::arg("temperature") = 1.0f)
+        .def("beam_search", &Decoder::beam_search, py::arg("input_ids"),
+             py::arg("beam_width") = 4, py::arg("max_new_tokens") = 32,
+             py::arg("eos_token_id") = -1, py::arg("length_penalty") = 1.0f,
+             py::arg("return_trace") = false, py::arg("trace_logits_ptr") = 0)
+        .def("beam_search_batch", &Decoder::beam_search_batch, py::arg("input_ids"),
+             py::arg("beam_width") = 4, py::arg("max_new_tokens") = 32,
+             py::arg("eos_token_id") = -1, py::arg("length_penalty") = 1.0f,
+             py::arg("return_trace") = false, py::arg("trace_logits_ptr") = 0)
         .def("begin_synthetic", &Decoder::begin_synthetic, py::arg("batch"),
              py::arg("context_len"), py::arg("seed") = 0, py::arg("shuffle") = true)
         .def("prefill", &Decoder::prefill, py::arg("row"), py::arg("tokens"))
@@ -527,6 +629,8 @@ PYBIND11_MODULE(llm_decoder, m) {
            py::arg("tile_id"), py::arg("layer") = 0)
       .def("set_eviction", &KVTileCache::set_eviction, py::arg("policy"))
       .def("fork", &KVTileCache::fork)
+      .def("reorder", &KVTileCache::reorder, py::arg("first_beam"), py::arg("parent"),
+           py::arg("n_tokens"))
       .def("release", &KVTileCache::release)
       .def("sync_page_table_to_gpu", &KVTileCache::sync_page_table_to_gpu)
       .def("save_to_file", &KVTileCache::save_to_file, py::arg("path"),
@@ -590,6 +694,22 @@ PYBIND11_MODULE(llm_decoder, m) {
         py::arg("workspace_bytes") = 0, py::arg("stream") = 0, py::arg("row_group") = 1,
         py::arg("eos_token") = -1, py::arg("eos_threshold") = 0.0f, py::arg("probs_out") = 0,
         py::arg("scores_out") = 0);
+  m.def("beam_select",
+        [](uintptr_t logits, uintptr_t score_in, int num_seqs, int W, int V, uintptr_t cand_score,
+           uintptr_t cand_parent, uintptr_t cand_token, uintptr_t stream) {
+          // beam_select_rows over device pointers: logits [num_seqs * W][V] and
+          // score_in [num_seqs * W] fp32 -> the best 2W (score, parent, token) per sequence
+          py::gil_scoped_release nogil;
+          check(beam_select_rows(reinterpret_cast<const float*>(logits),
+                                 reinterpret_cast<const float*>(score_in), num_seqs, W, V,
+                                 reinterpret_cast<float*>(cand_score),
+                                 reinterpret_cast<int32_t*>(cand_parent),
+                                 reinterpret_cast<int32_t*>(cand_token),
+                                 reinterpret_cast<void*>(stream)));
+        },
+        py::arg("logits"), py::arg("score_in"), py::arg("num_seqs"), py::arg("W"), py::arg("V"),
+        py::arg("cand_score"), py::arg("cand_parent"), py::arg("cand_token"),
+        py::arg("stream") = 0);
   m.def("dnnl_matmul_int8",
         [](uintptr_t A, uintptr_t B, uintptr_t C, int BATCH, int M, int N, int K, float scaleA,
            float scaleB, float scaleC, uintptr_t bias, const std::string& activation,

@@ -17,6 +17,9 @@
 // device memory, so replays need no re-capture.  Only page allocation (a new
 // page every page_size tokens, copy-on-write of forked pages) happens on the
 // host between replays and is pushed with kv_cache_sync().
+// Beam search (llm_decoder_beam_search) replays the same graph in beam mode:
+// the token choice is beam_select_rows' two launches, and between replays the
+// host ranks the hypotheses and re-parents the rows' pages (kv_cache_reorder).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -151,6 +154,15 @@ struct llm_decoder {
   float top_p = 1.f;
   uint64_t sample_seed = 0;
   bool use_graph = true;  // LLM_GRAPH=0: eager launches (per-kernel profiling)
+  // beam search (llm_decoder_beam_search): in beam mode the step's token choice
+  // is beam_select_rows' two launches over the rows' cumulative scores
+  // (beam_score, uploaded by the search between steps), whose 2W candidates
+  // per sequence run_step copies to h_cand: [score | parent | token] blocks of
+  // 2 * batch 4-byte items each.  Entering / leaving the mode re-captures the graph.
+  bool beam_mode = false;
+  DevBuf<float> beam_score, beam_ws, cand_score;
+  DevBuf<int32_t> cand_parent, cand_token;
+  std::vector<int32_t> h_cand;
   int qa_ld = 0;
   size_t b16 = 0;  // max_batch rounded up to 16-row tiles
 
@@ -245,6 +257,11 @@ static int create_decoder(const llm_decoder_config* cfg_in, int kv_dtype, llm_de
   LLM_HIP_RET(hipMemset(d->beam_ctr.p, 0, sizeof(unsigned) * d->beam_ctr.n));
   d->b16 = B16;
   RET_IF(d->tokens.alloc((size_t)B));
+  RET_IF(d->beam_score.alloc((size_t)B));
+  RET_IF(d->beam_ws.alloc(beam_select_ws_floats(B, 4)));  // (>= any num_seqs * W <= B)
+  RET_IF(d->cand_score.alloc((size_t)2 * B));
+  RET_IF(d->cand_parent.alloc((size_t)2 * B));
+  RET_IF(d->cand_token.alloc((size_t)2 * B));
   RET_IF(d->pos.alloc((size_t)B));
   RET_IF(d->ctx.alloc((size_t)B));
   d->pps = 0;  // balanced splits derived on device from each row's context
@@ -771,6 +788,15 @@ int llm_decoder::tap(int l, int stage, const Rows& R, int K, hipStream_t st) {
 int llm_decoder::next_tokens(const float* xr, int n, int r0, const int32_t* ctr, hipStream_t st,
                              int32_t* adv_pos, int32_t* adv_ctx) {
   float* lg = logits.p + (size_t)r0 * V;
+  if (beam_mode && adv_pos) {  // the decode step of a beam search (rows 0 .. batch - 1)
+    LLM_HIP_RET(launch_lm_head(xr, emb_packed.p, lg, n, V, hid, nullptr,
+                               lm_pi.p + (size_t)r0 * lm_nwg, st));
+    LLM_HIP_RET(launch_beam_select(lg, beam_score.p + r0, n / row_group, row_group, V,
+                                   cand_score.p + 2 * r0, cand_parent.p + 2 * r0,
+                                   cand_token.p + 2 * r0, beam_ws.p, st));
+    LLM_HIP_RET(launch_advance(adv_pos, adv_ctx, n, st));
+    return LLM_OK;
+  }
   const bool sample = temperature > 0.f && top_k != 1;
   float* pv = lm_pv.p + (size_t)r0 * lm_nwg;
   int32_t* pi = lm_pi.p + (size_t)r0 * lm_nwg;
@@ -859,6 +885,15 @@ int llm_decoder::run_step(const int32_t* tokens_host, float* logits_dev, int32_t
   if (logits_dev)
     LLM_HIP_RET(hipMemcpyAsync(logits_dev, logits.p, sizeof(float) * batch * V,
                                hipMemcpyDeviceToDevice, st));
+  if (beam_mode) {  // the candidates of num_seqs = batch / W sequences, 2W each
+    h_cand.resize((size_t)6 * batch);
+    const size_t nb = sizeof(int32_t) * 2 * batch;
+    LLM_HIP_RET(hipMemcpyAsync(h_cand.data(), cand_score.p, nb, hipMemcpyDeviceToHost, st));
+    LLM_HIP_RET(hipMemcpyAsync(h_cand.data() + 2 * batch, cand_parent.p, nb,
+                               hipMemcpyDeviceToHost, st));
+    LLM_HIP_RET(hipMemcpyAsync(h_cand.data() + 4 * batch, cand_token.p, nb,
+                               hipMemcpyDeviceToHost, st));
+  }
   if (next_host) {
     LLM_HIP_RET(hipMemcpyAsync(next_host, tokens.p, sizeof(int32_t) * batch,
                                hipMemcpyDeviceToHost, st));
@@ -1251,6 +1286,194 @@ extern "C" int llm_decoder_generate(llm_decoder* d, const int32_t* prompts,
   if (range_rc) return fail(LLM_ERR_RANGE, "llm_decoder_generate: the fused o_proj clamped a head "
                                            "product in at least one step; `out` is complete, the "
                                            "ids after that step may differ");
+  return LLM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// beam search (llm_decoder.h: llm_decoder_beam_search)
+// ---------------------------------------------------------------------------
+namespace {
+
+struct BeamHyp {
+  std::vector<int32_t> ids;
+  float sum = 0.f;    // cumulative log-probability (the device's fp32 score)
+  float score = 0.f;  // sum / len^alpha
+};
+
+float beam_final_score(float sum, size_t len, float alpha) {
+  return (float)((double)sum / std::pow((double)len, (double)alpha));
+}
+
+}  // namespace
+
+extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
+                                       const int32_t* prompt_lens, int prompt_stride,
+                                       int num_seqs, const llm_beam_options* opt,
+                                       int32_t* out_ids, int32_t* out_len,
+                                       float* out_sum_logprob, float* out_score) {
+  LLM_REQUIRE(d && prompts && prompt_lens && opt && out_ids && out_len && out_sum_logprob &&
+                  out_score,
+              "llm_decoder_beam_search: NULL");
+  const int W = opt->beam_width, max_new = opt->max_new_tokens;
+  LLM_REQUIRE(W >= 1 && W <= 4, "llm_decoder_beam_search: beam_width must be in [1, 4]");
+  LLM_REQUIRE(max_new >= 1, "llm_decoder_beam_search: max_new_tokens must be >= 1");
+  LLM_REQUIRE(opt->length_penalty >= 0.f && std::isfinite(opt->length_penalty),
+              "llm_decoder_beam_search: length_penalty must be finite and >= 0");
+  LLM_REQUIRE(opt->eos_token >= -1 && opt->eos_token < d->V,
+              "llm_decoder_beam_search: eos_token must be -1 or a token id");
+  LLM_REQUIRE(num_seqs >= 1 && (long long)num_seqs * W <= d->maxB,
+              "llm_decoder_beam_search: num_seqs * beam_width must be in [1, max_batch]");
+  LLM_REQUIRE(d->V >= 2 * W, "llm_decoder_beam_search: vocab_size < 2 * beam_width");
+  LLM_REQUIRE(d->V <= 65536, "llm_decoder_beam_search: vocab_size > 65536");
+  int max_len = 0;
+  for (int s = 0; s < num_seqs; ++s) {
+    LLM_REQUIRE(prompt_lens[s] >= 1 && prompt_lens[s] <= prompt_stride,
+                "llm_decoder_beam_search: every prompt needs >= 1 token");
+    for (int i = 0; i < prompt_lens[s]; ++i) {
+      const int t = prompts[(size_t)s * prompt_stride + i];
+      LLM_REQUIRE(t >= 0 && t < d->V, "llm_decoder_beam_search: token id out of range");
+    }
+    max_len = std::max(max_len, prompt_lens[s]);
+  }
+  LLM_REQUIRE(max_len + max_new - 1 <= d->cfg.max_seq_len,
+              "llm_decoder_beam_search: prompt + max_new_tokens exceeds max_seq_len");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->weights_ready, "llm_decoder_beam_search: weights not loaded");
+  // the step graph's token choice becomes the beam selection for the length
+  // of the search (a sampling mode is untouched: beam mode takes precedence)
+  struct ModeGuard {
+    llm_decoder* d;
+    ~ModeGuard() {
+      if (d->beam_mode) { d->beam_mode = false; d->graph_batch = -1; }
+    }
+  } mode_guard{d};
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  const int rows = num_seqs * W, K = 2 * W;
+  RET_IF(reset_rows(d, rows, 0));
+  // prompt[:-1] into beam 0's pages (the prefill's own token choice, argmax or
+  // a draw, is not used), shared with the other beams
+  for (int s = 0; s < num_seqs; ++s) {
+    const int b0 = s * W, n = prompt_lens[s] - 1;
+    if (n > 0) RET_IF(d->prefill(b0, prompts + (size_t)s * prompt_stride, n, d->stream));
+    for (int w = 1; w < W; ++w) {
+      if (n > 0) RET_IF(kv_cache_fork(d->kv, b0, b0 + w));
+      d->h_pos[b0 + w] = n;
+    }
+  }
+  std::vector<int32_t> pos(rows), ctx(rows), tok(rows), dummy(rows), parent(W);
+  std::vector<float> score(rows);
+  for (int r = 0; r < rows; ++r) {
+    pos[r] = d->h_pos[r];
+    ctx[r] = pos[r] + 1;
+    tok[r] = prompts[(size_t)(r / W) * prompt_stride + prompt_lens[r / W] - 1];
+    score[r] = r % W == 0 ? 0.f : -INFINITY;
+  }
+  LLM_HIP_RET(hipMemcpy(d->pos.p, pos.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice));
+  LLM_HIP_RET(hipMemcpy(d->ctx.p, ctx.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice));
+  d->row_group = W;
+  d->beam_mode = true;
+  d->graph_batch = -1;
+
+  std::vector<std::vector<BeamHyp>> finished(num_seqs);
+  std::vector<char> done(num_seqs, 0);
+  std::vector<std::vector<int32_t>> hist(rows), next_hist(W);
+  std::vector<float> next_score(W);
+  std::vector<int32_t> next_tok(W);
+  int range_rc = LLM_OK, steps = 0;
+  for (int st = 0; st < max_new; ++st) {
+    LLM_HIP_RET(hipMemcpyAsync(d->beam_score.p, score.data(), sizeof(float) * rows,
+                               hipMemcpyHostToDevice, d->stream));
+    float* lg = opt->trace_logits_dev ? opt->trace_logits_dev + (size_t)st * rows * d->V : nullptr;
+    // (next_host: the step waits for the device, so h_cand is complete, and
+    // reports a clamp of the fused o_proj as generate's steps do)
+    const int rc = d->run_step(tok.data(), lg, dummy.data(), d->stream);
+    if (rc == LLM_ERR_RANGE) range_rc = rc;
+    else RET_IF(rc);
+    steps = st + 1;
+    const float* cs = reinterpret_cast<const float*>(d->h_cand.data());
+    const int32_t* cp = d->h_cand.data() + 2 * rows;
+    const int32_t* ct = d->h_cand.data() + 4 * rows;
+    bool all_done = true;
+    for (int s = 0; s < num_seqs; ++s) {
+      const int b0 = s * W;
+      int live = 0;
+      for (int j = 0; j < K; ++j) {
+        const float sc = cs[(size_t)s * K + j];
+        const int32_t p = cp[(size_t)s * K + j], t = ct[(size_t)s * K + j];
+        if (opt->trace_cand_score) opt->trace_cand_score[((size_t)st * num_seqs + s) * K + j] = sc;
+        if (opt->trace_cand_parent) opt->trace_cand_parent[((size_t)st * num_seqs + s) * K + j] = p;
+        if (opt->trace_cand_token) opt->trace_cand_token[((size_t)st * num_seqs + s) * K + j] = t;
+        if (p < 0 || p >= W || t < 0 || t >= d->V)
+          return fail(LLM_ERR_HIP, "llm_decoder_beam_search: the device returned a candidate out "
+                                   "of range");
+        if (t == opt->eos_token) {
+          if (j < W && !done[s]) {
+            BeamHyp h;
+            h.ids = hist[b0 + p];
+            h.ids.push_back(t);
+            h.sum = sc;
+            h.score = beam_final_score(sc, h.ids.size(), opt->length_penalty);
+            finished[s].push_back(std::move(h));
+          }
+        } else if (live < W) {
+          parent[live] = p;
+          next_tok[live] = t;
+          next_score[live] = sc;
+          next_hist[live] = hist[b0 + p];
+          next_hist[live].push_back(t);
+          ++live;
+        }
+      }
+      if (live != W)
+        return fail(LLM_ERR_HIP, "llm_decoder_beam_search: fewer than beam_width live candidates");
+      for (int w = 0; w < W; ++w) {
+        hist[b0 + w].swap(next_hist[w]);
+        tok[b0 + w] = next_tok[w];
+        score[b0 + w] = next_score[w];
+        if (opt->trace_live_parent)
+          opt->trace_live_parent[((size_t)st * num_seqs + s) * W + w] = parent[w];
+        if (opt->trace_live_token)
+          opt->trace_live_token[((size_t)st * num_seqs + s) * W + w] = next_tok[w];
+      }
+      RET_IF(kv_cache_reorder(d->kv, b0, W, parent.data(), d->h_pos[b0]));
+      if ((int)finished[s].size() >= W) done[s] = 1;
+      all_done = all_done && done[s];
+    }
+    if (all_done) break;
+  }
+  if (opt->steps_run) *opt->steps_run = steps;
+  // the live beams of the last step: their scores for a later inspection, and
+  // the page table as the reorder left it
+  LLM_HIP_RET(hipMemcpyAsync(d->beam_score.p, score.data(), sizeof(float) * rows,
+                             hipMemcpyHostToDevice, d->stream));
+  LLM_HIP_RET(hipMemcpyAsync(d->tokens.p, tok.data(), sizeof(int32_t) * rows,
+                             hipMemcpyHostToDevice, d->stream));
+  RET_IF(kv_cache_sync(d->kv, d->stream));
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  for (int s = 0; s < num_seqs; ++s) {
+    std::vector<BeamHyp>& pool = finished[s];
+    if (!done[s])
+      for (int w = 0; w < W; ++w) {
+        BeamHyp h;
+        h.ids = hist[s * W + w];
+        h.sum = score[s * W + w];
+        h.score = beam_final_score(h.sum, h.ids.size(), opt->length_penalty);
+        pool.push_back(std::move(h));
+      }
+    std::stable_sort(pool.begin(), pool.end(),
+                     [](const BeamHyp& a, const BeamHyp& b) { return a.score > b.score; });
+    for (int w = 0; w < W; ++w) {
+      const BeamHyp& h = pool[w];
+      int32_t* o = out_ids + ((size_t)s * W + w) * max_new;
+      for (int i = 0; i < max_new; ++i) o[i] = i < (int)h.ids.size() ? h.ids[i] : -1;
+      out_len[s * W + w] = (int32_t)h.ids.size();
+      out_sum_logprob[s * W + w] = h.sum;
+      out_score[s * W + w] = h.score;
+    }
+  }
+  if (range_rc) return fail(LLM_ERR_RANGE, "llm_decoder_beam_search: the fused o_proj clamped a "
+                                           "head product in at least one step; the results are "
+                                           "complete, the ids after that step may differ");
   return LLM_OK;
 }
 

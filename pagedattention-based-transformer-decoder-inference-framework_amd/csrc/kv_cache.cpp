@@ -94,6 +94,8 @@ KvCache::~KvCache() {
   if (d_val) (void)hipFree(d_val);
   if (h_idx) (void)hipHostFree(h_idx);
   if (h_val) (void)hipHostFree(h_val);
+  if (d_pairs) (void)hipFree(d_pairs);
+  if (h_pairs) (void)hipHostFree(h_pairs);
   if (staging_done) (void)hipEventDestroy(staging_done);
 }
 
@@ -229,15 +231,56 @@ int KvCache::prepare_append(int beam, int pos) {
 
 int KvCache::sync(hipStream_t st) {
   // pending copy-on-write page copies first (old page -> new page; K and V
-  // are adjacent, one copy each)
-  for (const auto& c : cow) {
-    const size_t bytes = page_stride();
-    LLM_HIP_RET(hipMemcpyAsync((char*)k_pool + (size_t)c.second * bytes,
-                               (char*)k_pool + (size_t)c.first * bytes, bytes,
-                               hipMemcpyDeviceToDevice, st));
+  // are adjacent, one copy each).
+  // Two or more go in one launch (after a beam fork every child appends into
+  // the shared tail page: (W - 1) * L * H copies per sequence and step), unless
+  // a copy's destination is another's source -- a page copied, shared again
+  // and copied on, or freed and handed out again, between two syncs -- or the
+  // page is no whole number of 16-byte vectors: those keep the ordered memcpys.
+  bool staged = false;
+  bool batch = cow.size() > 1 && page_stride() % 16 == 0;
+  if (batch) {
+    std::vector<int32_t> srcs(cow.size()), dsts(cow.size());
+    for (size_t i = 0; i < cow.size(); ++i) srcs[i] = cow[i].first, dsts[i] = cow[i].second;
+    std::sort(srcs.begin(), srcs.end());
+    std::sort(dsts.begin(), dsts.end());
+    if (std::adjacent_find(dsts.begin(), dsts.end()) != dsts.end()) batch = false;  // written twice
+    for (size_t i = 0; batch && i < dsts.size(); ++i)
+      if (std::binary_search(srcs.begin(), srcs.end(), dsts[i])) batch = false;
   }
+  if (batch) {
+    const size_t np = cow.size();
+    LLM_HIP_RET(hipEventSynchronize(staging_done));  // previous staging consumed
+    if (np > pairs_cap) {
+      if (d_pairs) LLM_HIP_RET(hipFree(d_pairs));
+      if (h_pairs) LLM_HIP_RET(hipHostFree(h_pairs));
+      d_pairs = nullptr; h_pairs = nullptr;
+      pairs_cap = std::max<size_t>(np, 2048);
+      LLM_HIP_RET(hipMalloc(&d_pairs, pairs_cap * 2 * sizeof(int32_t)));
+      LLM_HIP_RET(hipHostMalloc(&h_pairs, pairs_cap * 2 * sizeof(int32_t), hipHostMallocDefault));
+    }
+    for (size_t i = 0; i < np; ++i) {
+      h_pairs[2 * i] = cow[i].first;
+      h_pairs[2 * i + 1] = cow[i].second;
+    }
+    LLM_HIP_RET(hipMemcpyAsync(d_pairs, h_pairs, np * 2 * sizeof(int32_t), hipMemcpyHostToDevice,
+                               st));
+    LLM_HIP_RET(launch_copy_pages(k_pool, page_stride(), d_pairs, (int)np, st));
+    staged = true;
+  } else {
+    for (const auto& c : cow) {
+      const size_t bytes = page_stride();
+      LLM_HIP_RET(hipMemcpyAsync((char*)k_pool + (size_t)c.second * bytes,
+                                 (char*)k_pool + (size_t)c.first * bytes, bytes,
+                                 hipMemcpyDeviceToDevice, st));
+    }
+  }
+  cow_pages += (long long)cow.size();
   cow.clear();
-  if (dirty.empty()) return LLM_OK;
+  if (dirty.empty()) {
+    if (staged) LLM_HIP_RET(hipEventRecord(staging_done, st));
+    return LLM_OK;
+  }
   const size_t n = dirty.size();
   if (n * 4 > entries) {  // mostly dirty: push the whole table
     LLM_HIP_RET(hipEventSynchronize(staging_done));
@@ -333,6 +376,12 @@ extern "C" long long kv_cache_free_pages(const kv_cache* c) {
   return c->impl.free_count();
 }
 
+extern "C" long long kv_cache_cow_copies(const kv_cache* c) {
+  if (!c) return -1;
+  std::lock_guard<std::mutex> g(const_cast<kv_cache*>(c)->impl.mu);
+  return c->impl.cow_pages;
+}
+
 extern "C" int kv_cache_assign(kv_cache* c, int layer, int beam, int head, int tile, int page) {
   LLM_REQUIRE(c, "kv_cache_assign: NULL");
   KvCache& k = c->impl;
@@ -426,6 +475,44 @@ extern "C" int kv_cache_fork(kv_cache* c, int src_beam, int dst_beam) {
         if (sp >= 0) k.refcount[sp] += 1;
         k.drop_page(dp);
         k.set_entry(di, sp);
+      }
+  return LLM_OK;
+}
+
+extern "C" int kv_cache_reorder(kv_cache* c, int first_beam, int n, const int32_t* parent,
+                                int n_tokens) {
+  LLM_REQUIRE(c && parent, "kv_cache_reorder: NULL");
+  KvCache& k = c->impl;
+  std::lock_guard<std::mutex> g(k.mu);
+  LLM_REQUIRE(n >= 1 && first_beam >= 0 && first_beam <= k.beams - n,
+              "kv_cache_reorder: rows first_beam .. first_beam + n - 1 must be beams of the cache");
+  LLM_REQUIRE(n_tokens >= 0, "kv_cache_reorder: n_tokens < 0");
+  const int nt = (n_tokens + k.TS - 1) / k.TS;
+  LLM_REQUIRE(nt <= k.max_tiles, "kv_cache_reorder: n_tokens exceeds max_tiles*page_size");
+  bool identity = true;
+  for (int i = 0; i < n; ++i) {
+    LLM_REQUIRE(parent[i] >= 0 && parent[i] < n, "kv_cache_reorder: parent out of range");
+    identity = identity && parent[i] == i;
+  }
+  if (identity) return LLM_OK;
+  // Tile by tile: read the n rows' entries, take the children's references,
+  // then drop what the rewritten slots held (in that order a page's count
+  // never touches zero while a child still wants it)
+  std::vector<int32_t> old(n);
+  for (int l = 0; l < k.L; ++l)
+    for (int h = 0; h < k.H; ++h)
+      for (int t = 0; t < nt; ++t) {
+        for (int i = 0; i < n; ++i) old[i] = k.h_table[k.index(l, first_beam + i, h, t)];
+        for (int i = 0; i < n; ++i) {
+          const int32_t np = old[parent[i]];
+          if (np != old[i] && np >= 0) k.refcount[np] += 1;
+        }
+        for (int i = 0; i < n; ++i) {
+          const int32_t np = old[parent[i]];
+          if (np == old[i]) continue;
+          k.drop_page(old[i]);
+          k.set_entry(k.index(l, first_beam + i, h, t), np);
+        }
       }
   return LLM_OK;
 }

@@ -43,6 +43,12 @@ struct KvCache {
   int32_t* h_val = nullptr;
   size_t staging_cap = 0;
   hipEvent_t staging_done = nullptr;
+  // (src, dst) page pairs of one sync's batched copy-on-write launch: pinned
+  // host staging and its device copy, guarded by staging_done like h_idx
+  int32_t* h_pairs = nullptr;
+  int32_t* d_pairs = nullptr;
+  size_t pairs_cap = 0;
+  long long cow_pages = 0;  // copy-on-write page copies issued so far (a counter for measurements)
   std::mutex mu;
   // kv_cache_set_eviction: LLM_EVICT_LRU makes register_tile evict the least
   // recently registered table entries when the pool is exhausted

@@ -346,6 +346,15 @@ __global__ void scatter_i32_kernel(int32_t* __restrict__ dst, const int64_t* __r
   if (i < n) dst[idx[i]] = val[i];
 }
 
+// Copy-on-write page copies of one kv_cache_sync in one launch: workgroup i
+// copies page pairs[2i] over page pairs[2i + 1] (bytes16 16-byte vectors each).
+__global__ __launch_bounds__(256) void copy_pages_kernel(u32x4* __restrict__ pool, size_t bytes16,
+                                                         const int32_t* __restrict__ pairs) {
+  const u32x4* src = pool + (size_t)pairs[2 * blockIdx.x] * bytes16;
+  u32x4* dst = pool + (size_t)pairs[2 * blockIdx.x + 1] * bytes16;
+  for (size_t i = threadIdx.x; i < bytes16; i += blockDim.x) dst[i] = src[i];
+}
+
 // Seeded random fp16 fill (synthetic KV contexts): splitmix64 -> ~N(0,1)*scale
 // via the sum of 4 uniforms (Irwin-Hall), cheap and deterministic.
 // Element i of the n = pages * page_elems lands at p[(i / page_elems) *
@@ -462,6 +471,15 @@ hipError_t launch_scatter_i32(int32_t* dst, const int64_t* idx, const int32_t* v
                               hipStream_t st) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(scatter_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, idx, val, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_pages(void* pool, size_t page_stride, const int32_t* pairs, int n,
+                             hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (page_stride % 16 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(copy_pages_kernel, dim3(n), dim3(256), 0, st, static_cast<u32x4*>(pool),
+                     page_stride / 16, pairs);
   return hipGetLastError();
 }
 

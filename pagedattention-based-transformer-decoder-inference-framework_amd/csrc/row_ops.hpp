@@ -43,6 +43,19 @@ hipError_t launch_argmax_partials(const float* part_val, const int32_t* part_idx
 hipError_t launch_sample(const float* logits, int rows, int row0, int V, float temperature,
                          int top_k, float top_p, uint64_t seed, const int32_t* counter,
                          int32_t* out, hipStream_t st);
+// Beam candidates (csrc/beam_select.hip, beam_select_rows in llm_decoder.h):
+// the row stage and the merge stage on `st`, both capturable.  ws: device
+// scratch of beam_select_ws_floats(num_seqs, W) floats (the row stage's
+// m, log(s + 1e-6) and 2W (logit, token) pairs per row).
+size_t beam_select_ws_floats(int num_seqs, int W);
+hipError_t launch_beam_select(const float* logits, const float* score_in, int num_seqs, int W,
+                              int V, float* cand_score, int32_t* cand_parent,
+                              int32_t* cand_token, float* ws, hipStream_t st);
+// pool[pairs[2i+1]] := pool[pairs[2i]] for i < n, pages of page_stride bytes
+// (a multiple of 16) at pool + page * page_stride: one workgroup per pair,
+// 16-byte loads and stores.  No destination may be another pair's source.
+hipError_t launch_copy_pages(void* pool, size_t page_stride, const int32_t* pairs, int n,
+                             hipStream_t st);
 // Seeded uniform (variance-1 x scale) fp16 over `pages` pages of page_elems
 // elements, page p at p + p * page_stride elements.
 hipError_t launch_fill_random_f16(void* p, size_t pages, size_t page_elems, size_t page_stride,

@@ -21,10 +21,9 @@
 // reductions per threshold, no sort.
 #include "common.hpp"
 #include "row_ops.hpp"
+#include "row_vals.hpp"
 
 namespace llm {
-
-constexpr int kSampleThreads = 512;  // 8 waves: 256 VGPRs per lane available
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
@@ -56,44 +55,6 @@ struct SampleArgs {
   int32_t* out;
   int32_t* out2;  // optional second destination (stride out2_stride)
   int out2_stride;
-};
-
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, T* sh, Op op) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = sh[0];
-  for (int i = 1; i < kSampleThreads / 64; ++i) t = op(t, sh[i]);  // fixed order
-  return t;
-}
-
-// Thread t owns the contiguous tokens [t*VPT, t*VPT + VPT) of the row.  The
-// first VPT_REG of them live in registers, the rest in LDS (VPT 128: 128 KiB,
-// [slot][thread] so each access is bank-conflict free).
-template <int VPT>
-struct RowVals {
-  // register slots; the rest in LDS: VPT 64 -> 32 + 64 KiB, VPT 128 -> 56 + 144 KiB
-  static constexpr int R = VPT <= 32 ? VPT : (VPT <= 64 ? 32 : 56);
-  float reg[R];
-  // volatile: re-read per use, so the compiler does not hoist the LDS half into
-  // registers across the radix-search loops (that spilled)
-  volatile float* lds;  // [(VPT - R)][kSampleThreads]
-  // f(i, value&): register slots unrolled, LDS slots in a rolled loop (dynamic
-  // LDS indexing is free; unrolling it only made the compiler hoist and spill)
-  template <typename F>
-  __device__ __forceinline__ void each(F f) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) f(i, reg[i]);
-#pragma unroll 1
-    for (int i = R; i < VPT; ++i) {
-      float v = lds[(i - R) * kSampleThreads + threadIdx.x];
-      f(i, v);
-      lds[(i - R) * kSampleThreads + threadIdx.x] = v;
-    }
-  }
 };
 
 template <int VPT>

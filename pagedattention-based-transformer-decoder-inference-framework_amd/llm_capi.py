@@ -45,6 +45,17 @@ class PaDecodeOptions(ctypes.Structure):
                 ("scores_out", c_void_p)]
 
 
+class LlmBeamOptions(ctypes.Structure):
+    """llm_beam_options: the trace pointers are host arrays ([steps][num_seqs][2W]
+    candidates, [steps][num_seqs][W] live beams) except trace_logits_dev."""
+    _fields_ = [("beam_width", ctypes.c_int), ("max_new_tokens", ctypes.c_int),
+                ("eos_token", ctypes.c_int), ("length_penalty", ctypes.c_float),
+                ("trace_cand_parent", c_void_p), ("trace_cand_token", c_void_p),
+                ("trace_cand_score", c_void_p), ("trace_live_parent", c_void_p),
+                ("trace_live_token", c_void_p), ("trace_logits_dev", c_void_p),
+                ("steps_run", ctypes.POINTER(ctypes.c_int))]
+
+
 class LlmError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"[llm status {status}] {msg}")
@@ -95,6 +106,13 @@ _SIGS = {
     "sample_rows": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, ctypes.c_uint64,
                             c_int, c_void_p, c_void_p]),
     "sample_uniform_host": (c_float, [ctypes.c_uint64, c_int, c_int]),
+    "beam_select_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "kv_cache_reorder": (c_int, [c_void_p, c_int, c_int, c_i32p, c_int]),
+    "kv_cache_cow_copies": (c_ll, [c_void_p]),
+    "llm_decoder_beam_search": (c_int, [c_void_p, c_i32p, c_i32p, c_int, c_int,
+                                        ctypes.POINTER(LlmBeamOptions), c_i32p, c_i32p,
+                                        ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "quantize_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "layernorm_quant": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
@@ -410,6 +428,30 @@ def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0, 
     check(lib.sample_rows(ptr(logits), R, V, temperature, top_k, top_p, seed, counter, ptr(out),
                           stream_ptr(stream)))
     return out
+
+
+def beam_select(logits, score_in, W, stream=None):
+    """beam_select_rows on torch device tensors: fp32 logits [num_seqs * W][V] and
+    cumulative scores [num_seqs * W] (-inf: beam not live) -> (cand_score fp32,
+    cand_parent int32, cand_token int32), each [num_seqs][2W], best first."""
+    import torch
+    lib = load()
+    R, V = logits.shape
+    if W < 1 or R % W:
+        raise ValueError("beam_select: rows must be num_seqs * W")
+    S = R // W
+    cs = torch.empty((S, 2 * W), dtype=torch.float32, device=logits.device)
+    cp = torch.empty((S, 2 * W), dtype=torch.int32, device=logits.device)
+    ct = torch.empty((S, 2 * W), dtype=torch.int32, device=logits.device)
+    check(lib.beam_select_rows(ptr(logits), ptr(score_in), S, W, V, ptr(cs), ptr(cp), ptr(ct),
+                               stream_ptr(stream)))
+    return cs, cp, ct
+
+
+def kv_cache_reorder(kv_handle, first_beam, parent, n_tokens) -> None:
+    """kv_cache_reorder on a kv_cache handle (KVTileCache.handle, decoder.kv_handle)."""
+    arr = (ctypes.c_int32 * len(parent))(*parent)
+    check(load().kv_cache_reorder(c_void_p(kv_handle), first_beam, len(parent), arr, n_tokens))
 
 
 def quantize_rows(x, stream=None):
