@@ -498,18 +498,23 @@ def sample_uniform(seed: int, row: int, counter: int) -> float:
     return float(np.float32(z >> 40) * np.float32(1.0 / 16777216.0))
 
 
-def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0):
+def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0,
+                neighbours=False):
     """Returns (tokens int32 [R], margin [R]): margin = relative distance of the
     draw from the nearest CDF boundary (small margins may legitimately differ
-    from a device run whose float sums are ordered differently)."""
+    from a device run whose float sums are ordered differently).  With
+    ``neighbours`` also int32 [R][2]: the kept tokens below and above that
+    nearest boundary, the only two a differently ordered sum may return."""
     logits = np.asarray(logits, np.float32)
     R, V = logits.shape
     toks = np.zeros(R, np.int32)
     margin = np.full(R, np.inf)
+    near = np.zeros((R, 2), np.int32)
     for r in range(R):
         row = logits[r]
         if temperature <= 0 or top_k == 1:
             toks[r] = int(np.argmax(row))  # first maximum
+            near[r] = toks[r]
             continue
         x = row / np.float32(temperature)
         e = np.exp((x - x.max()).astype(np.float32)).astype(np.float32)
@@ -536,6 +541,9 @@ def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0):
         i = int(np.searchsorted(cdf, target, side="right"))
         i = min(i, int(np.nonzero(q)[0][-1]))
         toks[r] = i
-        bnd = np.abs(cdf[q > 0] - target)
-        margin[r] = bnd.min() / max(Z, 1e-30)
-    return toks, margin
+        kept = np.nonzero(q)[0]
+        bnd = np.abs(cdf[kept] - target)  # cdf[kept[j]]: boundary between kept[j] and kept[j + 1]
+        j = int(np.argmin(bnd))
+        margin[r] = bnd[j] / max(Z, 1e-30)
+        near[r] = kept[j], kept[min(j + 1, len(kept) - 1)]
+    return (toks, margin, near) if neighbours else (toks, margin)

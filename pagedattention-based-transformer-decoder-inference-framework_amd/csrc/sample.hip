@@ -154,27 +154,34 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(SampleArgs 
   const int ctr = a.counter ? a.counter[r] : a.counter0;
   const float target = sample_uniform(a.seed, a.row0 + r, ctr) * Z;
   const float lo = threadIdx.x ? scan[threadIdx.x - 1] : 0.f;
-  // the thread whose [lo, lo + part) holds target picks inside its chunk
+  // The claims must tile [0, Z).  `lo + part` is one fp32 add and the next
+  // thread's lo another association of the same terms, an ulp apart often
+  // enough that a claim [lo, lo + part) left targets to nobody; nor is the scan
+  // monotone to the last bit.  So the owner is the FIRST thread with kept mass
+  // whose inclusive scan exceeds the target, else the last thread with kept
+  // mass: exactly one thread whenever any mass is kept.
+  const bool has = part > 0.f;
+  int own = has && target < scan[threadIdx.x] ? (int)threadIdx.x : 0x7fffffff;
+  own = block_reduce(own, shi, [](int x, int y) { return min(x, y); });
+  if (own == 0x7fffffff) {
+    own = block_reduce(has ? (int)threadIdx.x : -1, shi, [](int x, int y) { return max(x, y); });
+    if (own < 0) own = 0;  // no kept mass (a row of -inf or NaN only): thread 0 writes token 0
+  }
+  if ((int)threadIdx.x != own) return;
   int pick = 0x7fffffff;
-  if (part > 0.f && target >= lo && (target < lo + part || threadIdx.x == kSampleThreads - 1 ||
-                                     scan[threadIdx.x] >= Z)) {
-    float c = lo;
-    int last = -1;
-    p.each([&](int i, float& v) {  // ascending token index
-      if (v > 0.f) {
-        last = base + i;
-        c += v;
-        if (target < c && pick == 0x7fffffff) pick = base + i;
-      }
-    });
-    if (pick == 0x7fffffff) pick = last;  // rounding at the top of the range
-  }
-  pick = block_reduce(pick, shi, [](int x, int y) { return min(x, y); });
-  if (threadIdx.x == 0) {
-    const int tok = pick == 0x7fffffff ? 0 : pick;
-    a.out[r] = tok;
-    if (a.out2) a.out2[(size_t)r * a.out2_stride] = tok;
-  }
+  float c = lo;
+  int last = -1;
+  p.each([&](int i, float& v) {  // ascending token index
+    if (v > 0.f) {
+      last = base + i;
+      c += v;
+      if (target < c && pick == 0x7fffffff) pick = base + i;
+    }
+  });
+  if (pick == 0x7fffffff) pick = last;  // rounding at the top of the chunk
+  const int tok = pick < 0 ? 0 : pick;  // (only without kept mass)
+  a.out[r] = tok;
+  if (a.out2) a.out2[(size_t)r * a.out2_stride] = tok;
 }
 
 template <int VPT>

@@ -116,6 +116,15 @@ _SIGS = {
     "quantize_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "layernorm_quant": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    # tuning library only (csrc/tune/row_ops_tune.hip): the row launchers in the
+    # forms the decoder runs them (pack, embedding source, zero_x, fp16 output)
+    "layernorm_quant_tune": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p]),
+    "layernorm_f16_tune": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "quantize_rows_tune": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "to_f16_tune": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "kv_cache_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_ll,
                                 ctypes.POINTER(c_void_p)]),
     "kv_cache_create_typed": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_int,

@@ -713,3 +713,54 @@ def test_forced_hidden_2048_tile_forms(gpu, oracle, rows):
     _, worst, n_vals, n_flips = _forced_lockstep(dec, OracleDecoder(oracle, w, rows), taps,
                                                  prompts, gen=4, V=512)
     assert n_flips < 1e-3 * n_vals, (n_flips, n_vals)
+
+
+def _tied_vocab_decoder(oracle, cls, hid_heads, rows):
+    """A one-layer decoder whose embedding (and tied LM head) repeats 7 rows:
+    emb[v] = base[v % 7], so every logit row holds 7 distinct values, each
+    shared bit for bit by ~143 tokens spread over the whole vocabulary."""
+    V, D = 1000, 64
+    rng = np.random.default_rng(hid_heads + rows)
+    if cls == "INT8Decoder":
+        from oracle.oracle import synthetic_int8_model
+        w = synthetic_int8_model(oracle, L=1, H=hid_heads, D=D, V=V, max_seq=16, seed=3,
+                                 fast=hid_heads > 8)
+    else:
+        w = _f16_model(rng, 1, hid_heads, D, V, 16)
+    base = rng.standard_normal((7, hid_heads * D)).astype(np.float16)
+    w["emb"] = np.ascontiguousarray(base[np.arange(V) % 7])
+    return w, _make_gpu_decoder(w, max_batch=rows, cls=cls)
+
+
+@pytest.mark.parametrize("cls,heads,rows", [
+    ("INT8Decoder", 2, 1), ("INT8Decoder", 2, 17), ("INT8Decoder", 2, 33),
+    ("CUDADecoder", 2, 1), ("CUDADecoder", 2, 17), ("CUDADecoder", 2, 33),
+    ("INT8Decoder", 36, 1),  # hid 2304 > 2048: lm_head_kernel<1, 16, 1>
+])
+def test_greedy_ties_through_lm_head(gpu, oracle, cls, heads, rows):
+    """Greedy decode takes its token from the LM head's fused partial maxima
+    (lm_head_* kernels + argmax_partials_kernel), not from argmax_rows: with
+    the step's maximum logit shared bit for bit by ~143 tokens across lanes,
+    waves, vocabulary tiles and workgroups, the first of them wins, in the
+    1-, 2- and 4-row-tile forms (rows 1 / 17 / 33)."""
+    torch = _torch()
+    V = 1000
+    w, dec = _tied_vocab_decoder(oracle, cls, heads, rows)
+    dec.begin_synthetic(rows, 0, 0, False)
+    logits = torch.empty((rows, V), device="cuda")
+    tok = [(3 * r + 1) % V for r in range(rows)]
+    for step in range(2):
+        nxt = np.asarray(dec.step(tok, logits_ptr=logits.data_ptr(), want_next=True))
+        torch.cuda.synchronize()
+        lg = logits.cpu().numpy()
+        assert np.isfinite(lg).all()
+        bits = lg.view(np.uint32)
+        for r in range(rows):
+            tied = np.nonzero(bits[r] == bits[r, np.argmax(lg[r])])[0]
+            # precondition: the maximum is shared by one whole residue class
+            assert len(tied) in (142, 143) and len(set(tied % 7)) == 1, (r, len(tied))
+            assert tied[-1] > V - 8  # up to the last vocabulary tile and workgroup
+        want = np.argmax(lg, axis=1)  # first maximum
+        assert (want < 7).all()
+        np.testing.assert_array_equal(nxt, want)
+        tok = [int(t) + 7 * (r % 100) for r, t in enumerate(nxt)]  # same embedding, other ids
