@@ -637,20 +637,29 @@ size_t ln_lds_bytes(int K) {
 }
 constexpr size_t kLnLdsMax = 160 * 1024;
 
+// The kernel instantiation of one launch, as gemm_form chooses it:
+// gemm_kernel<KIND, mt, nt, waves, 0, prologue> on a grid of kslices k slices.
+struct GemmForm {
+  int mt;        // 16-row tiles per workgroup: 1, 2 or 4
+  int nt;        // 16-column tiles per workgroup: 1 or 2 (tuning build: also 3, 4)
+  int waves;     // waves per workgroup as launched: 8 or 4
+  int kslices;   // gridDim.z
+  int prologue;  // the LayerNorm / quantising prologue kernel (PRO = 1)
+};
+
 template <GemmKind KIND, int MT, int NT>
-hipError_t launch_gemm_nt(const GemmArgs& a, int waves, int mblocks, hipStream_t st, int kslices) {
+hipError_t launch_gemm_nt(const GemmArgs& a, const GemmForm& f, int mblocks, hipStream_t st) {
   const int ntiles = (a.N + 15) / 16;
-  const dim3 grid((ntiles + NT - 1) / NT, mblocks, kslices);
+  const dim3 grid((ntiles + NT - 1) / NT, mblocks, f.kslices);
   if constexpr (NT <= 2) {
-    if (a.ln_x) {
+    if (f.prologue) {
       const size_t lds = ln_lds_bytes<KIND, MT, NT, 8>(a.K);
       hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 1>), grid, dim3(512), lds, st, a);
       return hipGetLastError();
     }
   }
-  // the cross-wave sums' static LDS (WAVES x MT NT KiB) must stay <= 64 KiB
   if constexpr (MT * NT * 8 <= 64) {
-    if (waves != 4) {
+    if (f.waves == 8) {
       hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8>), grid, dim3(512), 0, st, a);
       return hipGetLastError();
     }
@@ -660,14 +669,13 @@ hipError_t launch_gemm_nt(const GemmArgs& a, int waves, int mblocks, hipStream_t
 }
 
 template <GemmKind KIND, int MT>
-hipError_t launch_gemm_mt(const GemmArgs& a, int NT, int waves, int mblocks, hipStream_t st,
-                          int kslices) {
+hipError_t launch_gemm_mt(const GemmArgs& a, const GemmForm& f, int mblocks, hipStream_t st) {
 #if LLM_TUNING
-  if (NT == 4 && !a.ln_x) return launch_gemm_nt<KIND, MT, 4>(a, waves, mblocks, st, kslices);
-  if (NT == 3 && !a.ln_x) return launch_gemm_nt<KIND, MT, 3>(a, waves, mblocks, st, kslices);
+  if (f.nt == 4) return launch_gemm_nt<KIND, MT, 4>(a, f, mblocks, st);
+  if (f.nt == 3) return launch_gemm_nt<KIND, MT, 3>(a, f, mblocks, st);
 #endif
-  return NT == 2 ? launch_gemm_nt<KIND, MT, 2>(a, waves, mblocks, st, kslices)
-                 : launch_gemm_nt<KIND, MT, 1>(a, waves, mblocks, st, kslices);
+  return f.nt == 2 ? launch_gemm_nt<KIND, MT, 2>(a, f, mblocks, st)
+                   : launch_gemm_nt<KIND, MT, 1>(a, f, mblocks, st);
 }
 
 }  // namespace
@@ -742,13 +750,15 @@ inline bool narrow_decode_tile(const GemmArgs& a, int kstep, TileChoice& t) {
   return narrow_tile_for(a.M, a.N, a.KS * kstep, t);
 }
 
-template <GemmKind KIND>
-hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t st, int nt_override = 0,
-                       int waves_override = 0, int mrows_override = 0, int ks_override = 0) {
-  GemmArgs a = a_in;
+// The form launch_gemm launches for `a` (kstep: the kind's KSTEP; overrides
+// 0 = automatic; reads only the shape, ln_x / ln_g, partial and ksplit2): the
+// one place the kernel instantiation is chosen.  launch_gemm dispatches on the
+// result and the tuning build reports it (gemm_form_tune).
+inline GemmForm gemm_form(const GemmArgs& a, int kstep, int nt_override = 0,
+                          int waves_override = 0, int mrows_override = 0, int ks_override = 0) {
   TileChoice tc{0, 0, 0};
   const bool narrow = nt_override == 0 && waves_override == 0 && mrows_override == 0 &&
-                      narrow_decode_tile(a, GemmTraits<KIND>::KSTEP, tc);
+                      narrow_decode_tile(a, kstep, tc);
   if (narrow) {
     nt_override = tc.nt;
     waves_override = tc.waves;
@@ -765,13 +775,34 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t st, int nt_override = 0
   // Infinity Cache); split-K fills them with k slices instead
   if (mrows == 64 && NT == 1 && (a.N + 15) / 16 < 256 && !a.ln_x && !a.partial) mrows = 32;
   if (mrows_override > 0) mrows = mrows_override;
-  const int ks = a.partial ? std::max(1, ks_override) : a.ksplit2 ? 2 : 1;
-  const int mblocks = (a.M + mrows - 1) / mrows;
-  const int tiles = ((a.N + 15) / 16 + NT - 1) / NT * mblocks;
-  if (a.xcd_map && (ks < 2 || 8 % ks != 0 || (tiles * ks) % 8 != 0)) a.xcd_map = 0;
-  if (mrows == 16) return launch_gemm_mt<KIND, 1>(a, NT, waves, mblocks, st, ks);
-  if (mrows == 32) return launch_gemm_mt<KIND, 2>(a, NT, waves, mblocks, st, ks);
-  return launch_gemm_mt<KIND, 4>(a, NT, waves, mblocks, st, ks);
+  GemmForm f{};
+  f.mt = mrows == 16 ? 1 : mrows == 32 ? 2 : 4;
+  // 3 / 4 column tiles: tuning build, and not with a prologue
+  f.nt = NT == 2 ? 2 : 1;
+#if LLM_TUNING
+  if ((NT == 3 || NT == 4) && !a.ln_x) f.nt = NT;
+#endif
+  // prologue kernels are always 8 waves; else 4 waves when requested, or where
+  // the 8-wave cross-wave sums' static LDS (WAVES x MT NT KiB) would pass 64 KiB
+  f.prologue = a.ln_x != nullptr;
+  f.waves = f.prologue || (f.mt * f.nt * 8 <= 64 && waves != 4) ? 8 : 4;
+  f.kslices = a.partial ? std::max(1, ks_override) : a.ksplit2 ? 2 : 1;
+  return f;
+}
+
+template <GemmKind KIND>
+hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t st, int nt_override = 0,
+                       int waves_override = 0, int mrows_override = 0, int ks_override = 0) {
+  GemmArgs a = a_in;
+  const GemmForm f = gemm_form(a, GemmTraits<KIND>::KSTEP, nt_override, waves_override,
+                               mrows_override, ks_override);
+  const int mblocks = (a.M + 16 * f.mt - 1) / (16 * f.mt);
+  const int tiles = ((a.N + 15) / 16 + f.nt - 1) / f.nt * mblocks;
+  if (a.xcd_map && (f.kslices < 2 || 8 % f.kslices != 0 || (tiles * f.kslices) % 8 != 0))
+    a.xcd_map = 0;
+  if (f.mt == 1) return launch_gemm_mt<KIND, 1>(a, f, mblocks, st);
+  if (f.mt == 2) return launch_gemm_mt<KIND, 2>(a, f, mblocks, st);
+  return launch_gemm_mt<KIND, 4>(a, f, mblocks, st);
 }
 
 }  // namespace

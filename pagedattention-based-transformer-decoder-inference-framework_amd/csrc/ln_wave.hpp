@@ -14,7 +14,11 @@
 // 1 KiB contiguous (fully coalesced), and every output is one dword (4 int8)
 // or 8 bytes (4 fp16) per chunk.  The reduction order does not depend on the
 // output type, and any CPL that covers the row gives the same bits (empty
-// chunks add exact zeros).
+// chunks add exact zeros).  It is the LayerNorm launch's order (ln_row_sum:
+// per-thread partials, the launch's four wave sums, then their fixed
+// combination), so a row's LN, int8 image and scale are the same bits whether
+// the launch or the GEMM prologue computes them -- whatever the batch size
+// (tests/test_weight_gemm_gpu.py compares the taps bit for bit, K <= 2048).
 #pragma once
 
 #include "common.hpp"
@@ -29,6 +33,41 @@ __device__ __forceinline__ float ln_wave_max(float x) {
   x = fmaxf(x, mov_dpp<0x140>(x));  // row_mirror
   x = fmaxf(x, __shfl_xor(x, 16, 64));
   return fmaxf(x, __shfl_xor(x, 32, 64));
+}
+
+// DPP move into the lanes of the 4-lane banks in BANKS; the others keep `old`.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ float ln_upd_dpp(float old, float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old),
+                                                               __builtin_bit_cast(int, x), CTRL,
+                                                               0xF, BANKS, false));
+}
+
+// The LayerNorm launch's block_sum_fast (row_ops.hip) in one wave: p[w] is
+// this lane's partial of launch wave w (chunks [64 w, 64 w + 64); zeros past
+// the row).  Each of the four sums pairs lane ^ 32, 16, 8, 4, 2, 1 in that
+// order, as the launch's wave_sum does -- the same bits -- and the four run in
+// lockstep, straight-line, so that their shuffles overlap: the prologue waits
+// on these chains.  lane ^ 8 and lane ^ 4 are two banked row shifts each
+// (row_shl: lane l reads l + n, row_shr: l - n) instead of shuffles through
+// the LDS crossbar.
+__device__ __forceinline__ float ln_row_sum(const float (&p)[4]) {
+  float t[4] = {p[0], p[1], p[2], p[3]};
+#pragma unroll
+  for (int w = 0; w < 4; ++w) t[w] += __shfl_xor(t[w], 32, 64);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) t[w] += __shfl_xor(t[w], 16, 64);
+#pragma unroll
+  for (int w = 0; w < 4; ++w)  // row_shl:8 | row_shr:8
+    t[w] += ln_upd_dpp<0x118, 0xC>(ln_upd_dpp<0x108, 0x3>(t[w], t[w]), t[w]);
+#pragma unroll
+  for (int w = 0; w < 4; ++w)  // row_shl:4 | row_shr:4
+    t[w] += ln_upd_dpp<0x114, 0xA>(ln_upd_dpp<0x104, 0x5>(t[w], t[w]), t[w]);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) t[w] += mov_dpp<0x4E>(t[w]);  // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int w = 0; w < 4; ++w) t[w] += mov_dpp<0xB1>(t[w]);  // quad_perm [1,0,3,2]
+  return (t[0] + t[1]) + (t[2] + t[3]);
 }
 
 template <int CPL>
@@ -79,21 +118,37 @@ __device__ __forceinline__ float ln_wave_compute(LnRow<CPL>& x, const LnRow<CPL>
                                                  const LnRow<CPL>& bt, int K, float eps) {
   const int lane = lane_id();
   const int K4 = K >> 2;
-  float s = 0.f;
+  // Lane l's chunk j = w + 4 i is chunk i of thread 64 w + l of the launch
+  // (chunk c = threadIdx.x + 256 i): the same per-thread partials, summed per
+  // launch wave w and combined as the launch does.  A chunk the launch's
+  // thread does not hold (VPT 1 at K <= 1024) lies past the row: it adds an
+  // exact +0 to a partial that is never -0, and the variance skips it.
+  float p[4];
 #pragma unroll
-  for (int j = 0; j < CPL; ++j) s += (x.v[j][0] + x.v[j][1]) + (x.v[j][2] + x.v[j][3]);
-  const float mean = group_sum<64>(s) / (float)K;
-  float vs = 0.f;
+  for (int w = 0; w < 4; ++w) {
+    p[w] = 0.f;
 #pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    if (64 * j + lane >= K4) continue;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = x.v[j][e] - mean;
-      vs = fmaf(d, d, vs);
+    for (int i = 0; w + 4 * i < CPL; ++i) {
+      const int j = w + 4 * i;
+      p[w] += (x.v[j][0] + x.v[j][1]) + (x.v[j][2] + x.v[j][3]);
     }
   }
-  const float var = group_sum<64>(vs) / (float)K;
+  const float mean = ln_row_sum(p) / (float)K;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    p[w] = 0.f;
+#pragma unroll
+    for (int i = 0; w + 4 * i < CPL; ++i) {
+      const int j = w + 4 * i;
+      if (64 * j + lane >= K4) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = x.v[j][e] - mean;
+        p[w] = fmaf(d, d, p[w]);
+      }
+    }
+  }
+  const float var = ln_row_sum(p) / (float)K;
   const float inv_std = (float)(1.0 / (double)sqrtf(var + eps));
   float am = 0.f;
 #pragma unroll

@@ -171,7 +171,9 @@ __global__ __launch_bounds__(kRowThreads) void quantize_rows_v_kernel(
 // memory round trip;
 // wave DPP sums + one LDS exchange per reduction.  Numerics of
 // LayerNorm<T>::forward (decoder/layer_norm.hpp:20-37) and int8_quant.cpp as
-// ln_wave.hpp (the GEMM prologue); only the fp32 summation order differs.
+// ln_wave.hpp (the GEMM prologue), which follows this kernel's fp32 summation
+// order (per-thread partials, wave_sum, block_sum_fast's combination): change
+// one and the other must follow, or a row's bits depend on the batch size.
 // q / out16 in packed-A order when pack.
 template <int VPT>
 __global__ __launch_bounds__(kRowThreads) void layernorm_rows_kernel(

@@ -2,7 +2,9 @@
 // libllm_decoder_hip.so): GEMM entries with forced tile forms, split-K
 // slices, phase clocks and the one-launch seam experiment, for the scripts
 // that price them (scripts/tune_gemm*.py, gemm_phases.py, seam_pair.py) and
-// the tile-form exactness tests (tests/test_gemm_gpu.py).
+// the tile-form exactness tests (tests/test_gemm_gpu.py); and the decoder's
+// weight_gemm, its prologue predicates and the form launch_gemm picks behind
+// C entries (weight_gemm_tune ..., tests/test_weight_gemm_gpu.py).
 #include "gemm_impl.hpp"
 
 using namespace llm;
@@ -194,4 +196,104 @@ extern "C" int f16_gemm_tune(int nt, int waves, int mrows, int a_packed, const v
   a.C = C; a.c_cols = N; a.c_ld = N;
   hipError_t e = launch_gemm<GemmKind::F16>(a, as_stream(stream), nt, waves, mrows);
   return e == hipSuccess ? LLM_OK : fail(LLM_ERR_HIP, "f16_gemm_tune");
+}
+
+// llm::weight_gemm itself (argument translation and checks included) behind a
+// plain-C struct: every field of WeightGemm and, with has_kv, of KvAppendView
+// (ctypes mirror: llm_capi.WeightGemmTuneArgs), for tests/test_weight_gemm_gpu.py.
+// No kernel code here.
+struct WeightGemmTuneArgs {
+  int dtype;
+  const void* A;
+  int lda, a_packed;
+  const void* W_packed;
+  int M, N, K;
+  const float* sa;
+  const float* sw;
+  const float* bias;
+  int act;
+  float* C;
+  int c_cols, c_ld;
+  void* C16;
+  const float* ln_x;
+  const void* ln_emb;
+  const int32_t* ln_tok;
+  int ln_V;
+  const float* ln_g;
+  const float* ln_b;
+  float ln_eps;
+  void* act_out;
+  float* sa_out;
+  int w_keep, ln_quant_only, ksplit2;
+  int has_kv;  // 0: WeightGemm::kv = NULL
+  const int32_t* kv_pos;
+  const int32_t* kv_page_table;
+  const int32_t* kv_rows;
+  void* kv_k_pool;
+  void* kv_v_pool;
+  int kv_num_beams, kv_max_tiles, kv_page_size, kv_num_pages, kv_H, kv_D;
+  long long kv_page_stride;
+  int kv_dtype;
+  float kv_k_inv_scale, kv_v_inv_scale;
+};
+
+extern "C" int weight_gemm_tune(const WeightGemmTuneArgs* t, void* stream) {
+  LLM_REQUIRE(t, "weight_gemm_tune: NULL arguments");
+  KvAppendView kv;
+  kv.pos = t->kv_pos;
+  kv.page_table = t->kv_page_table;
+  kv.rows = t->kv_rows;
+  kv.k_pool = t->kv_k_pool;
+  kv.v_pool = t->kv_v_pool;
+  kv.num_beams = t->kv_num_beams; kv.max_tiles = t->kv_max_tiles;
+  kv.page_size = t->kv_page_size; kv.num_pages = t->kv_num_pages;
+  kv.H = t->kv_H; kv.D = t->kv_D;
+  kv.page_stride = (size_t)t->kv_page_stride;
+  kv.kv_dtype = t->kv_dtype;
+  kv.k_inv_scale = t->kv_k_inv_scale; kv.v_inv_scale = t->kv_v_inv_scale;
+  WeightGemm g;
+  g.dtype = t->dtype;
+  g.A = t->A; g.lda = t->lda; g.a_packed = t->a_packed;
+  g.W_packed = t->W_packed;
+  g.M = t->M; g.N = t->N; g.K = t->K;
+  g.sa = t->sa; g.sw = t->sw; g.bias = t->bias; g.act = t->act;
+  g.C = t->C; g.c_cols = t->c_cols; g.c_ld = t->c_ld;
+  g.C16 = t->C16;
+  g.kv = t->has_kv ? &kv : nullptr;
+  g.ln_x = t->ln_x;
+  g.ln_emb = static_cast<const _Float16*>(t->ln_emb);
+  g.ln_tok = t->ln_tok; g.ln_V = t->ln_V;
+  g.ln_g = t->ln_g; g.ln_b = t->ln_b; g.ln_eps = t->ln_eps;
+  g.act_out = t->act_out; g.sa_out = t->sa_out;
+  g.w_keep = t->w_keep;
+  g.ln_quant_only = t->ln_quant_only;
+  g.ksplit2 = t->ksplit2;
+  return weight_gemm(g, as_stream(stream));
+}
+
+extern "C" int gemm_ln_fusable_tune(int dtype, int M, int K) { return ln_fusable(dtype, M, K); }
+
+extern "C" int gemm_quant_prologue_ok_tune(int M, int N, int K) {
+  return quant_prologue_ok(M, N, K);
+}
+
+// The form (gemm_form) launch_gemm launches for an M x N x K GEMM of dtype:
+// form[5] = {16-row tiles, column tiles, waves launched, k slices, prologue}.
+// prologue: 0 none, 1 LayerNorm, 2 quantising; nt / waves / mrows: forced form
+// (0 = automatic) as i8_gemm_tune / f16_gemm_tune take it.
+extern "C" int gemm_form_tune(int dtype, int M, int N, int K, int prologue, int ksplit2, int nt,
+                              int waves, int mrows, int* form) {
+  LLM_REQUIRE(form && M > 0 && N > 0 && K > 0 && (dtype == LLM_I8 || dtype == LLM_F16) &&
+                  prologue >= 0 && prologue <= 2,
+              "gemm_form_tune: bad arguments");
+  const int kstep = dtype == LLM_I8 ? 64 : 32;
+  static const float never_read = 0.f;  // ln_x / ln_g only as flags
+  GemmArgs a{};
+  a.M = M; a.N = N; a.K = K; a.KS = K / kstep;
+  a.ln_x = prologue ? &never_read : nullptr;
+  a.ln_g = prologue == 1 ? &never_read : nullptr;
+  a.ksplit2 = ksplit2;
+  const GemmForm f = gemm_form(a, kstep, nt, waves, mrows);
+  form[0] = f.mt; form[1] = f.nt; form[2] = f.waves; form[3] = f.kslices; form[4] = f.prologue;
+  return LLM_OK;
 }

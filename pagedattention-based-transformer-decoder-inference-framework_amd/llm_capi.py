@@ -38,6 +38,26 @@ class PaKvView(ctypes.Structure):
                 ("kv_dtype", ctypes.c_int32), ("page_stride", ctypes.c_int64)]
 
 
+class WeightGemmTuneArgs(ctypes.Structure):
+    """weight_gemm_tune's argument (csrc/tune/gemm_tune.hip, tuning library only):
+    every field of the decoder's WeightGemm and, with has_kv, of KvAppendView
+    (csrc/gemm.hpp); zero-initialised fields are the structs' defaults except
+    ln_eps, kv_dtype (LLM_F16 is 0) and the inverse scales."""
+    _fields_ = [("dtype", c_int), ("A", c_void_p), ("lda", c_int), ("a_packed", c_int),
+                ("W_packed", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int),
+                ("sa", c_void_p), ("sw", c_void_p), ("bias", c_void_p), ("act", c_int),
+                ("C", c_void_p), ("c_cols", c_int), ("c_ld", c_int), ("C16", c_void_p),
+                ("ln_x", c_void_p), ("ln_emb", c_void_p), ("ln_tok", c_void_p), ("ln_V", c_int),
+                ("ln_g", c_void_p), ("ln_b", c_void_p), ("ln_eps", c_float),
+                ("act_out", c_void_p), ("sa_out", c_void_p), ("w_keep", c_int),
+                ("ln_quant_only", c_int), ("ksplit2", c_int), ("has_kv", c_int),
+                ("kv_pos", c_void_p), ("kv_page_table", c_void_p), ("kv_rows", c_void_p),
+                ("kv_k_pool", c_void_p), ("kv_v_pool", c_void_p), ("kv_num_beams", c_int),
+                ("kv_max_tiles", c_int), ("kv_page_size", c_int), ("kv_num_pages", c_int),
+                ("kv_H", c_int), ("kv_D", c_int), ("kv_page_stride", c_ll),
+                ("kv_dtype", c_int), ("kv_k_inv_scale", c_float), ("kv_v_inv_scale", c_float)]
+
+
 class PaDecodeOptions(ctypes.Structure):
     _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int),
                 ("top_p", ctypes.c_float), ("eos_token", ctypes.c_int),
@@ -125,6 +145,14 @@ _SIGS = {
                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "quantize_rows_tune": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "to_f16_tune": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    # tuning library only (csrc/tune/gemm_tune.hip): the decoder's weight_gemm,
+    # its prologue predicates, the form launch_gemm picks and the forced forms
+    "weight_gemm_tune": (c_int, [ctypes.POINTER(WeightGemmTuneArgs), c_void_p]),
+    "gemm_ln_fusable_tune": (c_int, [c_int, c_int, c_int]),
+    "gemm_quant_prologue_ok_tune": (c_int, [c_int, c_int, c_int]),
+    "gemm_form_tune": (c_int, [c_int] * 9 + [c_i32p]),
+    "f16_gemm_tune": (c_int, [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 3 +
+                      [c_void_p]),
     "kv_cache_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_ll,
                                 ctypes.POINTER(c_void_p)]),
     "kv_cache_create_typed": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_int,
