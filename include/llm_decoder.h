@@ -176,6 +176,46 @@ int pa_prefill(const pa_kv_view* kv, const float* q, int q_stride, float* out, i
                int row, int p0, int m, float sm_scale, void* workspace, size_t workspace_bytes,
                void* stream);
 
+/* pa_prefill over prompt chunks of SEVERAL sequences in one launch.  The m =
+ * sum(len) query rows are dense in q / out (strides and alignment as
+ * pa_prefill) and made of nseg segments in the order given: segment j is len
+ * consecutive rows at positions p0 .. p0+len-1 of page-table row `row`, whose
+ * K/V are already in that row's pages.  A page-table row appears in at most
+ * one segment.  Row i of segment j equals pa_prefill(row, p0, len) row i; in
+ * the one-pass form bit for bit (a query's result does not depend on the
+ * other queries of its tile).
+ * The launch is driven by a tile table, one entry {q0, nq, row, p0} per
+ * workgroup column: nq <= 64 rows from packed row q0, at positions p0 .. of
+ * page-table row `row`; a segment of length len gets ceil(len / 64) tiles and
+ * no tile straddles two segments.  pa_prefill_packed_tiles (host only) fills
+ * tiles[cap][4] and returns the tile count -- also when cap is too small or
+ * tiles is NULL, then writing nothing -- or < 0 for an invalid segment list.
+ * workspace is always required: it holds the tile table and the rows' context
+ * lengths, and at the split = 1 size also the split partials.  With at least
+ * pa_prefill_packed_workspace_bytes(.., 1) (and out_stride H*D) the key range
+ * is split -- one split length for the launch, planned as pa_prefill's from
+ * the longest segment end and the tile count; a tile skips the splits past
+ * its last query -- and merged as pa_decode's splits; with at least the
+ * split = 0 size it runs in one pass; with less, LLM_ERR_INVALID.
+ * LLM_ERR_INVALID (on the host, before any launch) also for nseg < 1, a
+ * segment with len < 1 or p0 < 0, a row outside the table or repeated,
+ * positions past max_tiles, and strides or alignment pa_prefill refuses;
+ * LLM_ERR_UNSUPPORTED for pools pa_prefill does not take.
+ * `segs` may be freed when the call returns: the table and the context
+ * lengths are written in stream order by small launches that carry the
+ * segment descriptors as kernel arguments, which the launch call copies (no
+ * host-to-device copy from the caller's memory is left in flight).  The call
+ * must not be captured into a graph: the nodes would carry this call's segment
+ * list, and the entry makes no promise about its launch count. */
+typedef struct pa_prefill_seg { int32_t row, p0, len; } pa_prefill_seg;
+int pa_prefill_packed_tiles(const pa_kv_view* kv, const pa_prefill_seg* segs, int nseg,
+                            int32_t* tiles, int cap);
+size_t pa_prefill_packed_workspace_bytes(const pa_kv_view* kv, const pa_prefill_seg* segs,
+                                         int nseg, int split);
+int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                      int out_stride, const pa_prefill_seg* segs, int nseg, float sm_scale,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* The optional stages of the reference attention, CPUAttentionInput /
  * CPUAttentionOutput (attention_cpu/attention_cpu.hpp:8-43) as used by
  * cpu_paged_attention_forward (attention_cpu/cpu_attention_kernel.cpp:37-129):
@@ -556,6 +596,27 @@ int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts, const int32_
  * row's next token from the last token's logits, so llm_decoder_step(tokens =
  * NULL) continues decoding.  llm_decoder_generate uses it for every prompt. */
 int llm_decoder_prefill(llm_decoder* d, int row, const int32_t* tokens, int n);
+
+/* Packed prefill: llm_decoder_prefill of several rows at once.  Row rows[i]
+ * (active, distinct) gets the next lens[i] >= 0 ids of `tokens` (host, the
+ * rows' ids concatenated; 0 skips the row).  The tokens go through layer
+ * passes of <= 512 PACKED tokens, filled greedily in row order: a pass holds
+ * segments of several rows (every weight GEMM at M = the pass, one
+ * pa_prefill_packed launch per layer; the decode kernel where
+ * llm_decoder_prefill_kernel is LLM_PREFILL_DECODE), a long prompt continues
+ * in the next pass and a row is never in one pass twice.  Each row ends as
+ * after llm_decoder_prefill: its next token chosen from its last token's
+ * logits.  Every argument is checked before the first launch (rows active and
+ * distinct, ids in range, position + len < max_seq_len): on LLM_ERR_INVALID no
+ * row has moved. */
+int llm_decoder_prefill_rows(llm_decoder* d, const int32_t* rows, const int32_t* tokens,
+                             const int32_t* lens, int nrows);
+/* on != 0: llm_decoder_generate and the prompt set-up of
+ * llm_decoder_beam_search prefill all their rows through
+ * llm_decoder_prefill_rows; 0 (the default): row by row, exactly as before.
+ * llm_decoder_prefill is unaffected.  The getter returns the switch (-1: NULL). */
+int llm_decoder_set_packed_prefill(llm_decoder* d, int on);
+int llm_decoder_packed_prefill(const llm_decoder* d);
 
 /* Token choice of every following step: greedy argmax (temperature <= 0 or
  * top_k == 1; the default, sample_from_logits, decoder/cuda_decoder.cu:7-14)

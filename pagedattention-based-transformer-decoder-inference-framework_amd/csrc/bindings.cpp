@@ -19,7 +19,10 @@
 // (llm_decoder_beam_search: [(ids, score), ...] per prompt, best first; what
 // api/router.py's stream_chat_beam loops greedy generate for), the module-level
 // beam_select (beam_select_rows), set_weights (host numpy arrays), low-level
-// begin_synthetic / step for the bench, PageTable / KVTileCache classes with
+// begin_synthetic / step for the bench, prefill(row, tokens) and its packed
+// form prefill_batch(rows, token_lists) (llm_decoder_prefill_rows) with the
+// read/write packed_prefill switch that generate* / beam_search* follow
+// (llm_decoder_set_packed_prefill, default False), PageTable / KVTileCache classes with
 // the kv_cache/ API names (page_table.hpp:5-37, kv_tile_cache.hpp:9-41) and
 // paged_attention() over raw device pointers.
 //
@@ -273,6 +276,22 @@ class Decoder {
     py::gil_scoped_release nogil;
     check(llm_decoder_prefill(d_, row, tokens.data(), (int)tokens.size()));
   }
+
+  // llm_decoder_prefill_rows: the prompts of several rows through shared passes
+  void prefill_batch(const std::vector<int32_t>& rows,
+                     const std::vector<std::vector<int32_t>>& tokens) {
+    if (rows.size() != tokens.size())
+      throw std::invalid_argument("prefill_batch: one token list per row");
+    std::vector<int32_t> lens, flat;
+    for (const auto& t : tokens) {
+      lens.push_back((int32_t)t.size());
+      flat.insert(flat.end(), t.begin(), t.end());
+    }
+    py::gil_scoped_release nogil;
+    check(llm_decoder_prefill_rows(d_, rows.data(), flat.data(), lens.data(), (int)rows.size()));
+  }
+  bool packed_prefill() const { return llm_decoder_packed_prefill(d_) == 1; }
+  void set_packed_prefill(bool on) { check(llm_decoder_set_packed_prefill(d_, on ? 1 : 0)); }
 
   void set_sampling(float temperature, int top_k, float top_p, uint64_t seed) {
     py::gil_scoped_release nogil;
@@ -576,6 +595,8 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("begin_synthetic", &Decoder::begin_synthetic, py::arg("batch"),
              py::arg("context_len"), py::arg("seed") = 0, py::arg("shuffle") = true)
         .def("prefill", &Decoder::prefill, py::arg("row"), py::arg("tokens"))
+        .def("prefill_batch", &Decoder::prefill_batch, py::arg("rows"), py::arg("tokens"))
+        .def_property("packed_prefill", &Decoder::packed_prefill, &Decoder::set_packed_prefill)
         .def("set_sampling", &Decoder::set_sampling, py::arg("temperature"),
              py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("seed") = 0)
         .def("begin_beams", &Decoder::begin_beams, py::arg("num_seqs"), py::arg("beam_width"),

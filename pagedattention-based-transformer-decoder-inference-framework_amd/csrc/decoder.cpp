@@ -186,10 +186,17 @@ struct llm_decoder {
   static constexpr int kPrefillChunk = 512;
   DevBuf<float> px, pq, po, ph1, psa;
   DevBuf<uint8_t> pact, pws;
-  DevBuf<int32_t> pmeta;  // [4][chunk]: pos, ctx, page-table row, token
+  DevBuf<int32_t> pmeta;  // [4][chunk]: pos, ctx, page-table row, token; then the
+                          // packed passes' tile table [<= chunk][4]
   size_t pws_bytes = 0;
   int pf_cap = 0;
+  int prefill_reserve(int C);
   int prefill(int row, const int32_t* toks, int n, hipStream_t st);
+  // llm_decoder_set_packed_prefill: generate / beam_search prefill all their
+  // rows through prefill_rows
+  bool packed_prefill = false;
+  int prefill_rows(const int32_t* rows, const int32_t* toks, const int32_t* lens, int nrows,
+                   hipStream_t st);
 };
 
 static int check_cfg(const llm_decoder_config& c) {
@@ -478,6 +485,16 @@ struct Rows {
   // row prefill_row, attended causally by the MFMA prefill kernel
   int prefill_row = -1;
   int prefill_p0 = 0;
+  // packed prefill pass (prefill_ntile > 0): the n rows are segments of several
+  // page-table rows (pos / ctx / beam_rows say which, per row), attended by one
+  // pa_prefill_packed launch over the device tile table prefill_tiles (ctx is
+  // its context_lens; attn_ws takes the split partials)
+  const int32_t* prefill_tiles = nullptr;
+  int prefill_ntile = 0;
+  int prefill_maxend = 0;  // the longest segment's end
+  // a prefill pass of either kind: no LN prologue fusion, no quantising
+  // prologue, no fused o_proj, no fc2 split, no taps
+  bool is_prefill() const { return prefill_row >= 0 || prefill_ntile > 0; }
   uint8_t* attn_ws = nullptr;
   size_t attn_ws_bytes = 0;
   // FP16 decode rows: the o_proj runs inside the attention's workgroup merge
@@ -538,7 +555,7 @@ int llm_decoder::layer_norm_into(WeightGemm& g, const Rows& R, const float* gamm
   LnSource src = embed_src;
   embed_src = LnSource{};
   src.zero_x = zero_x;  // (the LayerNorm launch only: the caller checks fc2_split)
-  if (R.prefill_row < 0 && ln_fusable(wdtype, R.n, hid)) {
+  if (!R.is_prefill() && ln_fusable(wdtype, R.n, hid)) {
     g.ln_x = R.x; g.ln_g = gamma; g.ln_b = beta; g.ln_eps = 1e-5f;
     g.ln_emb = src.emb; g.ln_tok = src.tok; g.ln_V = src.V;
     if (tap_q) { g.act_out = R.act; g.sa_out = R.sa; }  // the taps read A and the scales back
@@ -559,7 +576,7 @@ int llm_decoder::layer_norm_into(WeightGemm& g, const Rows& R, const float* gamm
 // launch.  Beam groups keep the merge launch (the beam kernel's workgroups
 // are 4 beams of one split), as do prefill chunks.
 bool llm_decoder::quant_prologue(const Rows& R) const {
-  return wdtype == LLM_I8 && R.prefill_row < 0 && R.row_group == 1 &&
+  return wdtype == LLM_I8 && !R.is_prefill() && R.row_group == 1 &&
          quant_prologue_ok(R.n, hid, hid);
 }
 
@@ -571,7 +588,7 @@ bool llm_decoder::quant_prologue(const Rows& R) const {
 // Needs the workgroup-merge form (2..8 splits), head_dim <= 128 and <= 64
 // heads; otherwise the o_proj GEMM runs as before.
 bool llm_decoder::oproj_fusable(const Rows& R) {
-  if (wdtype != LLM_F16 || kvt != LLM_F16 || R.prefill_row >= 0 || R.row_group != 1 ||
+  if (wdtype != LLM_F16 || kvt != LLM_F16 || R.is_prefill() || R.row_group != 1 ||
       R.beam_rows || !wo_heads.p ||
       D > 128 || H > 64 || !oproj_fuse_on())
     return false;
@@ -590,7 +607,7 @@ bool llm_decoder::oproj_fusable(const Rows& R) {
 // o_proj input -- in place of split + pa_merge_row_kernel (C5: 5 splits of
 // 103 pages -> 8 of 65 merged in the workgroup).
 bool llm_decoder::wgm_quant_ok(const Rows& R) {
-  if (wdtype != LLM_I8 || R.prefill_row >= 0 || R.row_group != 1 || R.beam_rows ||
+  if (wdtype != LLM_I8 || R.is_prefill() || R.row_group != 1 || R.beam_rows ||
       quant_prologue(R))
     return false;
   Rows r = R;
@@ -613,7 +630,7 @@ bool llm_decoder::wgm_quant_ok(const Rows& R) {
 // workgroup of the one-slice form reads all of A, 1 MB, the k slices half of
 // it (gemm_impl.hpp narrow_decode_tile).
 bool llm_decoder::fc2_split(const Rows& R) const {
-  return wdtype == LLM_I8 && R.prefill_row < 0 &&
+  return wdtype == LLM_I8 && !R.is_prefill() &&
          (R.n <= 16 || (R.n > 32 && R.n <= 64 && inter >= 16384)) &&
          !ln_fusable(wdtype, R.n, hid) && inter / 64 >= 16;
 }
@@ -639,7 +656,7 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
   pa_kv_view view;
   PaRequest rq;
   RET_IF(attn_request(R, &view, &rq, l));
-  if (R.prefill_row >= 0 && pa_prefill_supported(&view)) {
+  if (R.is_prefill() && pa_prefill_supported(&view)) {
     // one MFMA pass over the chunk (K/V pages read once per 32 queries), then
     // the o_proj input conversion the decode merge would have fused
     PaRowOutputs ro;
@@ -653,8 +670,12 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
     }
     // LLM_FP8 pages: the scales enter as in the decode launch below
     ro.out_scale = v_scale[l];
-    return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n,
-                               kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale,
+    const float sm = kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale;
+    if (R.prefill_ntile > 0)
+      return pa_prefill_packed_internal(&view, R.q, hid, R.o, hid, R.prefill_tiles,
+                                        R.prefill_ntile, R.ctx, R.n, R.prefill_maxend, sm,
+                                        R.attn_ws, R.attn_ws_bytes, st, &ro);
+    return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n, sm,
                                R.attn_ws, R.attn_ws_bytes, st, &ro);
   }
   // the request's pointers; the fp32 rows (R.o) are only needed by a
@@ -765,7 +786,7 @@ Rows llm_decoder::step_rows(int r0, int n, uint8_t* ws) {
 // FP16 decoders: the four packed fp16 GEMM inputs (2 bytes per element, no
 // scales); stage 3 (fc2's input) is act2, written by the fc1 epilogue.
 int llm_decoder::tap(int l, int stage, const Rows& R, int K, hipStream_t st) {
-  if (!tap_q || R.prefill_row >= 0 || R.beam_rows) return LLM_OK;
+  if (!tap_q || R.is_prefill() || R.beam_rows) return LLM_OK;
   const bool f16 = wdtype == LLM_F16;
   const size_t es = f16 ? 2 : 1;
   const size_t slot = (size_t)l * 4 + stage;
@@ -934,6 +955,34 @@ int llm_decoder::oproj_range_status() {
   return report_range(f);
 }
 
+// The prefill buffers for passes of up to C rows (kept; grown on demand).
+int llm_decoder::prefill_reserve(int C) {
+  if (C > pf_cap) {
+    const size_t C16 = ((size_t)C + 15) / 16 * 16;
+    RET_IF(px.alloc((size_t)C * hid));
+    RET_IF(pq.alloc((size_t)C * hid));
+    RET_IF(po.alloc((size_t)C * hid));
+    RET_IF(ph1.alloc((size_t)C * inter));
+    RET_IF(psa.alloc((size_t)C));
+    RET_IF(pact.alloc(C16 * std::max(hid, inter) * (wdtype == LLM_I8 ? 1 : 4)));  // F16: act, act2
+    RET_IF(pmeta.alloc((size_t)8 * C));
+    pws_bytes = 16;
+    for (int b = 1; b <= C; ++b)
+      pws_bytes = std::max(pws_bytes, pa_decode_workspace_bytes(b, H, D, max_tiles, 0));
+    {  // the MFMA prefill's split partials (its split count is bounded at any p0)
+      pa_kv_view v0;
+      RET_IF(kv_cache_view(kv, 0, &v0));
+      for (int b = 1; b <= C; ++b)
+        pws_bytes = std::max(pws_bytes, pa_prefill_ws_bytes(&v0, cfg.max_seq_len - b, b));
+      // ... and a packed pass's, whatever its segments
+      pws_bytes = std::max(pws_bytes, pa_prefill_packed_part_bound(&v0, C));
+    }
+    RET_IF(pws.alloc(pws_bytes));
+    pf_cap = C;
+  }
+  return LLM_OK;
+}
+
 // Chunked prefill of `n` prompt tokens of active row `row` (the reference's
 // is_prefill pass, attention/attention_cuda.hpp:21): the chunk's tokens are
 // the rows of one layer pass — M = chunk-size weight GEMMs, the K/V of every
@@ -949,27 +998,7 @@ int llm_decoder::prefill(int row, const int32_t* toks, int n, hipStream_t st) {
   LLM_REQUIRE(h_pos[row] + n < cfg.max_seq_len, "prefill: prompt exceeds max_seq_len");
   for (int i = 0; i < n; ++i) LLM_REQUIRE(toks[i] >= 0 && toks[i] < V, "prefill: token id out of range");
   const int C = std::min(n, kPrefillChunk);
-  if (C > pf_cap) {
-    const size_t C16 = ((size_t)C + 15) / 16 * 16;
-    RET_IF(px.alloc((size_t)C * hid));
-    RET_IF(pq.alloc((size_t)C * hid));
-    RET_IF(po.alloc((size_t)C * hid));
-    RET_IF(ph1.alloc((size_t)C * inter));
-    RET_IF(psa.alloc((size_t)C));
-    RET_IF(pact.alloc(C16 * std::max(hid, inter) * (wdtype == LLM_I8 ? 1 : 4)));  // F16: act, act2
-    RET_IF(pmeta.alloc((size_t)4 * C));
-    pws_bytes = 16;
-    for (int b = 1; b <= C; ++b)
-      pws_bytes = std::max(pws_bytes, pa_decode_workspace_bytes(b, H, D, max_tiles, 0));
-    {  // the MFMA prefill's split partials (its split count is bounded at any p0)
-      pa_kv_view v0;
-      RET_IF(kv_cache_view(kv, 0, &v0));
-      for (int b = 1; b <= C; ++b)
-        pws_bytes = std::max(pws_bytes, pa_prefill_ws_bytes(&v0, cfg.max_seq_len - b, b));
-    }
-    RET_IF(pws.alloc(pws_bytes));
-    pf_cap = C;
-  }
+  RET_IF(prefill_reserve(C));
   KvCache* k = kv_impl(kv);
   std::vector<int32_t> meta((size_t)4 * C), pc(2);
   for (int c0 = 0; c0 < n; c0 += C) {
@@ -1013,6 +1042,125 @@ int llm_decoder::prefill(int row, const int32_t* toks, int n, hipStream_t st) {
       LLM_HIP_RET(hipMemcpyAsync(ctx.p + row, &pc[1], sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
     LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc staging reused next chunk
+  }
+  return LLM_OK;
+}
+
+// Packed prefill (llm_decoder_prefill_rows): the prompts of several active rows
+// through shared layer passes.  A pass is up to kPrefillChunk packed tokens,
+// filled greedily in row order -- segments (row, p0, len) of different rows, a
+// long prompt continuing in the next pass at its new position, so a row is in
+// a pass at most once.  Everything in a layer pass is row-wise (pmeta carries
+// each packed row's position, context, page-table row and token) except the
+// MFMA attention, which takes the pass's tile table (pa_prefill_packed); rows
+// whose last token is in the pass get their next token from that packed row.
+int llm_decoder::prefill_rows(const int32_t* rows, const int32_t* toks, const int32_t* lens,
+                              int nrows, hipStream_t st) {
+  LLM_REQUIRE(weights_ready, "prefill_rows: weights not loaded");
+  LLM_REQUIRE(nrows >= 0 && (nrows == 0 || (rows && lens)), "prefill_rows: NULL argument");
+  long long total = 0;
+  {
+    std::vector<char> seen(batch, 0);
+    for (int i = 0; i < nrows; ++i) {
+      LLM_REQUIRE(rows[i] >= 0 && rows[i] < batch, "prefill_rows: row is not active");
+      LLM_REQUIRE(!seen[rows[i]], "prefill_rows: a row is given twice");
+      seen[rows[i]] = 1;
+      LLM_REQUIRE(lens[i] >= 0, "prefill_rows: negative length");
+      LLM_REQUIRE((long long)h_pos[rows[i]] + lens[i] < cfg.max_seq_len,
+                  "prefill_rows: prompt exceeds max_seq_len");
+      total += lens[i];
+    }
+    LLM_REQUIRE(total == 0 || toks, "prefill_rows: tokens is NULL");
+    for (long long i = 0; i < total; ++i)
+      LLM_REQUIRE(toks[i] >= 0 && toks[i] < V, "prefill_rows: token id out of range");
+  }
+  if (total == 0) return LLM_OK;
+  const int C = (int)std::min<long long>(total, kPrefillChunk);
+  RET_IF(prefill_reserve(C));
+  const int CAP = pf_cap;  // pmeta's array stride
+  pa_kv_view v0;
+  RET_IF(kv_cache_view(kv, 0, &v0));
+  KvCache* k = kv_impl(kv);
+  std::vector<int32_t> meta((size_t)8 * CAP), pc((size_t)2 * nrows);
+  std::vector<pa_prefill_seg> segs;
+  std::vector<int> seg_src;  // index into rows / lens of each segment
+  int ri = 0;                // the row being packed, `done` of its tokens placed
+  int done = 0;
+  long long tok0 = 0;        // its first token in toks
+  while (ri < nrows) {
+    segs.clear();
+    seg_src.clear();
+    int m = 0, maxend = 0;
+    while (ri < nrows && m < C) {
+      const int left = lens[ri] - done;
+      if (left == 0) {
+        tok0 += lens[ri];
+        ++ri, done = 0;
+        continue;
+      }
+      const int len = std::min(left, C - m), row = rows[ri], p0 = h_pos[row];
+      for (int i = 0; i < len; ++i) {
+        meta[m + i] = p0 + i;
+        meta[CAP + m + i] = p0 + i + 1;
+        meta[2 * CAP + m + i] = row;
+        meta[3 * CAP + m + i] = toks[tok0 + done + i];
+      }
+      segs.push_back(pa_prefill_seg{row, p0, len});
+      seg_src.push_back(ri);
+      m += len;
+      maxend = std::max(maxend, p0 + len);
+      done += len;
+      if (done < lens[ri]) break;  // the pass is full; the row continues in the next
+      tok0 += lens[ri];
+      ++ri, done = 0;
+    }
+    if (m == 0) break;
+    const int nseg = (int)segs.size();
+    const int ntile = pa_prefill_packed_tiles(&v0, segs.data(), nseg, meta.data() + 4 * CAP, CAP);
+    LLM_REQUIRE(ntile >= 1 && ntile <= CAP, "prefill_rows: bad segment list");
+    {
+      std::lock_guard<std::mutex> gk(k->mu);
+      for (const pa_prefill_seg& s : segs)
+        for (int t = s.p0; t < s.p0 + s.len; t = (t / TS + 1) * TS) RET_IF(k->prepare_append(s.row, t));
+      RET_IF(k->sync(st));
+    }
+    LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), ((size_t)4 * CAP + 4 * ntile) * sizeof(int32_t),
+                               hipMemcpyHostToDevice, st));
+    Rows R;
+    R.n = m;
+    R.x = px.p; R.q = pq.p; R.o = po.p; R.h1 = ph1.p; R.act = pact.p; R.sa = psa.p;
+    if (wdtype == LLM_F16)
+      R.act2 = pact.p + (((size_t)CAP + 15) / 16 * 16) * std::max(hid, inter) * 2;
+    R.pos = pmeta.p; R.ctx = pmeta.p + CAP; R.beam_rows = pmeta.p + 2 * CAP;
+    R.prefill_tiles = pmeta.p + 4 * CAP;
+    R.prefill_ntile = ntile;
+    R.prefill_maxend = maxend;
+    R.attn_ws = pws.p; R.attn_ws_bytes = pws_bytes;
+    LLM_HIP_RET(launch_embed(emb.p, pmeta.p + 3 * CAP, m, hid, V, px.p, st));
+    embed_src = LnSource{};  // (a failed step enqueue could have left it set)
+    for (int l = 0; l < L; ++l) {
+      RET_IF(layer_pre(l, st, R));
+      RET_IF(layer_attn(l, st, R));
+      RET_IF(layer_post(l, st, R));
+    }
+    int q0 = 0;
+    for (int j = 0; j < nseg; ++j) {
+      const pa_prefill_seg& s = segs[j];
+      const int src = seg_src[j], last = q0 + s.len - 1;
+      h_pos[s.row] = s.p0 + s.len;
+      // the row's last token: logits -> its next token, decode state
+      if (src < ri) {
+        RET_IF(next_tokens(px.p + (size_t)last * hid, 1, s.row, pmeta.p + last, st));
+        pc[2 * src] = s.p0 + s.len;
+        pc[2 * src + 1] = s.p0 + s.len + 1;
+        LLM_HIP_RET(hipMemcpyAsync(pos.p + s.row, &pc[2 * src], sizeof(int32_t),
+                                   hipMemcpyHostToDevice, st));
+        LLM_HIP_RET(hipMemcpyAsync(ctx.p + s.row, &pc[2 * src + 1], sizeof(int32_t),
+                                   hipMemcpyHostToDevice, st));
+      }
+      q0 += s.len;
+    }
+    LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc staging reused next pass
   }
   return LLM_OK;
 }
@@ -1107,6 +1255,24 @@ extern "C" int llm_decoder_prefill(llm_decoder* d, int row, const int32_t* token
   LLM_REQUIRE(d, "llm_decoder_prefill: NULL");
   std::lock_guard<std::mutex> g(d->mu);
   return d->prefill(row, tokens, n, d->stream);
+}
+
+extern "C" int llm_decoder_prefill_rows(llm_decoder* d, const int32_t* rows, const int32_t* tokens,
+                                        const int32_t* lens, int nrows) {
+  LLM_REQUIRE(d, "llm_decoder_prefill_rows: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  return d->prefill_rows(rows, tokens, lens, nrows, d->stream);
+}
+
+extern "C" int llm_decoder_set_packed_prefill(llm_decoder* d, int on) {
+  LLM_REQUIRE(d, "llm_decoder_set_packed_prefill: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  d->packed_prefill = on != 0;
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_packed_prefill(const llm_decoder* d) {
+  return d ? (d->packed_prefill ? 1 : 0) : -1;
 }
 
 extern "C" int llm_decoder_set_sampling(llm_decoder* d, float temperature, int top_k, float top_p,
@@ -1268,9 +1434,20 @@ extern "C" int llm_decoder_generate(llm_decoder* d, const int32_t* prompts,
   RET_IF(reset_rows(d, batch, 0));
   // every prompt but its last token goes through chunked prefill; decode steps
   // then run all rows in lockstep, each at its own position
-  for (int b = 0; b < batch; ++b)
-    if (prompt_lens[b] > 1)
-      RET_IF(d->prefill(b, prompts + (size_t)b * prompt_stride, prompt_lens[b] - 1, d->stream));
+  if (d->packed_prefill) {  // ... all rows through shared passes
+    std::vector<int32_t> prow(batch), plen(batch), ptok;
+    for (int b = 0; b < batch; ++b) {
+      prow[b] = b;
+      plen[b] = prompt_lens[b] - 1;
+      const int32_t* pb = prompts + (size_t)b * prompt_stride;
+      ptok.insert(ptok.end(), pb, pb + plen[b]);
+    }
+    RET_IF(d->prefill_rows(prow.data(), ptok.data(), plen.data(), batch, d->stream));
+  } else {
+    for (int b = 0; b < batch; ++b)
+      if (prompt_lens[b] > 1)
+        RET_IF(d->prefill(b, prompts + (size_t)b * prompt_stride, prompt_lens[b] - 1, d->stream));
+  }
   // a step whose fused o_proj clamped (LLM_ERR_RANGE) still produced its ids:
   // generation runs to the end, fills `out`, and then returns the status
   std::vector<int32_t> tok(batch), next(batch);
@@ -1352,9 +1529,20 @@ extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
   RET_IF(reset_rows(d, rows, 0));
   // prompt[:-1] into beam 0's pages (the prefill's own token choice, argmax or
   // a draw, is not used), shared with the other beams
+  if (d->packed_prefill) {  // every sequence's beam 0 through shared passes
+    std::vector<int32_t> prow(num_seqs), plen(num_seqs), ptok;
+    for (int s = 0; s < num_seqs; ++s) {
+      prow[s] = s * W;
+      plen[s] = prompt_lens[s] - 1;
+      const int32_t* pb = prompts + (size_t)s * prompt_stride;
+      ptok.insert(ptok.end(), pb, pb + plen[s]);
+    }
+    RET_IF(d->prefill_rows(prow.data(), ptok.data(), plen.data(), num_seqs, d->stream));
+  }
   for (int s = 0; s < num_seqs; ++s) {
     const int b0 = s * W, n = prompt_lens[s] - 1;
-    if (n > 0) RET_IF(d->prefill(b0, prompts + (size_t)s * prompt_stride, n, d->stream));
+    if (n > 0 && !d->packed_prefill)
+      RET_IF(d->prefill(b0, prompts + (size_t)s * prompt_stride, n, d->stream));
     for (int w = 1; w < W; ++w) {
       if (n > 0) RET_IF(kv_cache_fork(d->kv, b0, b0 + w));
       d->h_pos[b0 + w] = n;

@@ -117,6 +117,21 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
                         int out_stride, int row, int p0, int m, float sm_scale, void* workspace,
                         size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows = nullptr);
 
+// The packed form (C entry pa_prefill_packed): m dense rows of q / out made of
+// segments of several sequences, driven by a device tile table
+// tiles_dev[ntile][4] = {q0, nq, row, p0} (pa_prefill_packed_tiles) and the
+// rows' device context lengths ctx_dev[m] (position + 1); maxend = the longest
+// segment's end.  part_ws (pa_prefill_packed_part_bytes, or the bound over any
+// launch of up to max_rows rows) selects the split form as workspace does above.
+size_t pa_prefill_packed_meta_bytes(int m, int ntile);
+size_t pa_prefill_packed_part_bytes(const pa_kv_view* kv, int maxend, int ntile, int m);
+size_t pa_prefill_packed_part_bound(const pa_kv_view* kv, int max_rows);
+int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                               int out_stride, const int32_t* tiles_dev, int ntile,
+                               const int32_t* ctx_dev, int m, int maxend, float sm_scale,
+                               void* part_ws, size_t part_bytes, hipStream_t st,
+                               const PaRowOutputs* rows = nullptr);
+
 // Bytes from page p to page p + 1 of a view's pools (page_stride 0 = dense).
 inline size_t kv_view_page_stride(const pa_kv_view& v) {
   return v.page_stride > 0 ? (size_t)v.page_stride

@@ -41,6 +41,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "common.hpp"
 #include "pa_decode.hpp"
@@ -60,6 +61,10 @@ struct PaPrefillArgs {
   const int32_t* pt_row;  // page_table + row * H * max_tiles
   int H, max_tiles, num_pages;
   int p0, m;
+  // packed form (PACKED kernels): blockIdx.x indexes tiles[ntile][4] =
+  // {q0, nq, row, p0} (device), pt_row is unused and m is the packed row count
+  const int32_t* tiles;
+  const int32_t* page_table;
   float qscale;  // sm_scale * log2(e)
   // key-range split (blockIdx.z = split s: tiles [s*pps, (s+1)*pps)); with
   // part_acc the unnormalised state goes to the decode layout
@@ -92,7 +97,11 @@ __device__ __forceinline__ u32x2 fp8x4_to_f16(uint32_t w) {
       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))};
 }
 
-template <int KVT, int D, int TS, int NW>
+// PACKED: the workgroup's query tile comes from the tile table (rows q0 ..
+// q0+nq-1 of q / out are positions p0 .. of page-table row `row`) instead of
+// blockIdx.x * 16 NW of the one sequence; everything after these five values
+// is the same code.
+template <int KVT, int D, int TS, int NW, bool PACKED>
 __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   static_assert(KVT == LLM_F16 || KVT == LLM_FP8, "KV element type");
   constexpr bool FP8 = KVT == LLM_FP8;
@@ -118,16 +127,29 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   const int g = lane >> 4;
   const int c = lane & 15;
   const int h = blockIdx.y;
-  const int qbase = blockIdx.x * 16 * NW;
-  const int qi = qbase + w * 16 + c;  // this lane's query (column of S^T / O^T)
-  const int qpos = a.p0 + qi;
-  const int lastpos = a.p0 + min(qbase + 16 * NW, a.m) - 1;  // last key any query here sees
+  int q0, nq, p0;  // the tile: first row of q / out, rows, position of the first
+  const int32_t* pt_row;
+  if constexpr (PACKED) {
+    const int4 t = *reinterpret_cast<const int4*>(a.tiles + 4 * (size_t)blockIdx.x);
+    q0 = t.x, nq = t.y, p0 = t.w;
+    pt_row = a.page_table + (size_t)t.z * a.H * a.max_tiles;
+  } else {
+    q0 = blockIdx.x * 16 * NW;
+    nq = min(16 * NW, a.m - q0);
+    p0 = a.p0 + q0;
+    pt_row = a.pt_row;
+  }
+  const int qt = w * 16 + c;   // this lane's query of the tile (column of S^T / O^T)
+  const int qi = q0 + qt;      // its row of q / out
+  const bool qok = qt < nq;
+  const int qpos = p0 + qt;
+  const int lastpos = p0 + nq - 1;  // last key any query here sees
   const int split = blockIdx.z;
   const int kb0 = split * a.pps * TS / KB;
   const int nblk = min((split + 1) * a.pps * TS / KB, lastpos / KB + 1);
   // no query of this workgroup reaches this split: the merge never reads it
   if (kb0 >= nblk) return;
-  const int32_t* pt = a.pt_row + (size_t)h * a.max_tiles;
+  const int32_t* pt = pt_row + (size_t)h * a.max_tiles;
 
   // Q^T B-operand fragments: lane holds q[qi][32kk + 8g .. +7] (pre-scaled by
   // qscale), hi + lo.  The query's values are also scaled by a power of two
@@ -138,7 +160,7 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
 #pragma unroll
   for (int kk = 0; kk < NKK; ++kk) {
     f32x4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = x0;
-    if (qi < a.m) {
+    if (qok) {
       const float* qp = a.q + (size_t)qi * a.q_stride + h * D + 32 * kk + 8 * g;
       x0 = *reinterpret_cast<const f32x4*>(qp);
       x1 = *reinterpret_cast<const f32x4*>(qp + 4);
@@ -287,7 +309,7 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   // the 4 lanes of a query hold partial sums over their keys
   lrun += __shfl_xor(lrun, 16, 64);
   lrun += __shfl_xor(lrun, 32, 64);
-  if (qi < a.m) {
+  if (qok) {
     if (a.part_acc) {  // split partial state (unnormalised, log2 units)
       const size_t pidx = ((size_t)qi * a.H + h) * a.nsplit + split;
       float* o = a.part_acc + pidx * D + 4 * g;
@@ -306,23 +328,31 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   }
 }
 
+// ntile > 0: the packed form, one workgroup column per entry of a.tiles
+// (tiles of 16 * kPackedNW queries).
 template <int KVT, int D, int TS>
-hipError_t launch_prefill(const PaPrefillArgs& a, int nw, hipStream_t st) {
-  if (nw == 4) {
+hipError_t launch_prefill(const PaPrefillArgs& a, int nw, int ntile, hipStream_t st) {
+  if (ntile > 0) {
+    const dim3 grid(ntile, a.H, a.nsplit);
+    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 4, true>), grid, dim3(256), 0, st, a);
+  } else if (nw == 4) {
     const dim3 grid((a.m + 63) / 64, a.H, a.nsplit);
-    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 4>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 4, false>), grid, dim3(256), 0, st, a);
   } else {
     const dim3 grid((a.m + 31) / 32, a.H, a.nsplit);
-    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 2>), grid, dim3(128), 0, st, a);
+    hipLaunchKernelGGL((pa_prefill_kernel<KVT, D, TS, 2, false>), grid, dim3(128), 0, st, a);
   }
   return hipGetLastError();
 }
 
 template <int KVT>
-hipError_t launch_prefill_shape(const PaPrefillArgs& a, int D, int TS, int nw, hipStream_t st) {
+hipError_t launch_prefill_shape(const PaPrefillArgs& a, int D, int TS, int nw, int ntile,
+                                hipStream_t st) {
   if (D == 64)
-    return TS == 16 ? launch_prefill<KVT, 64, 16>(a, nw, st) : launch_prefill<KVT, 64, 32>(a, nw, st);
-  return TS == 16 ? launch_prefill<KVT, 128, 16>(a, nw, st) : launch_prefill<KVT, 128, 32>(a, nw, st);
+    return TS == 16 ? launch_prefill<KVT, 64, 16>(a, nw, ntile, st)
+                    : launch_prefill<KVT, 64, 32>(a, nw, ntile, st);
+  return TS == 16 ? launch_prefill<KVT, 128, 16>(a, nw, ntile, st)
+                  : launch_prefill<KVT, 128, 32>(a, nw, ntile, st);
 }
 
 // Launch geometry: NW waves (16 queries each) per workgroup; the key range is
@@ -333,17 +363,14 @@ constexpr int kTargetWgs = 1024;
 struct PrefillPlan {
   int nw, nsplit, pps;
 };
-PrefillPlan prefill_plan(const pa_kv_view* kv, int p0, int m) {
+// The key split of nq query tiles whose longest key range ends at position
+// `end` (exclusive); p.nw is set by the caller.
+PrefillPlan split_plan(const pa_kv_view* kv, int end, int nq, int nw) {
   PrefillPlan p;
-#if LLM_TUNING
-  p.nw = env_int("LLM_PREFILL_NW", 4) == 2 ? 2 : 4;
-#else
-  p.nw = 4;
-#endif
+  p.nw = nw;
   const int TS = kv->page_size;
   const int step = kKeyBlock / TS;  // tiles per key block
-  const int ntiles = (p0 + m + TS - 1) / TS;
-  const int nq = (m + 16 * p.nw - 1) / (16 * p.nw);
+  const int ntiles = (end + TS - 1) / TS;
   const int want = std::min(std::max(kTargetWgs / std::max(nq * kv->num_heads, 1), 1), 128);
   int pps = (ntiles + want - 1) / want;
   pps = std::max((pps + step - 1) / step * step, 2 * step);
@@ -354,6 +381,15 @@ PrefillPlan prefill_plan(const pa_kv_view* kv, int p0, int m) {
     p.nsplit = (ntiles + p.pps - 1) / p.pps;
   }
   return p;
+}
+
+PrefillPlan prefill_plan(const pa_kv_view* kv, int p0, int m) {
+#if LLM_TUNING
+  const int nw = env_int("LLM_PREFILL_NW", 4) == 2 ? 2 : 4;
+#else
+  const int nw = 4;
+#endif
+  return split_plan(kv, p0 + m, (m + 16 * nw - 1) / (16 * nw), nw);
 }
 
 }  // namespace
@@ -426,8 +462,8 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
   a.out_scale = out_scale;
   const int TS = kv->page_size;
   const hipError_t e = kv->kv_dtype == LLM_FP8
-                           ? launch_prefill_shape<LLM_FP8>(a, D, TS, pl.nw, st)
-                           : launch_prefill_shape<LLM_F16>(a, D, TS, pl.nw, st);
+                           ? launch_prefill_shape<LLM_FP8>(a, D, TS, pl.nw, 0, st)
+                           : launch_prefill_shape<LLM_F16>(a, D, TS, pl.nw, 0, st);
   if (e != hipSuccess) return fail(LLM_ERR_HIP, std::string("pa_prefill launch: ") + hipGetErrorString(e));
   if (split)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, (rows && !rows->keep_out) ? nullptr : out,
@@ -442,7 +478,243 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
   return LLM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// packed form: the chunks of several sequences in one launch
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kPackedTile = 16 * 4;  // queries per tile-table entry (the NW = 4 kernel)
+
+// The tile table and the rows' context lengths of up to kMetaSegs segments,
+// written on the device from segment descriptors that travel as kernel
+// arguments: the launch copies them, so the host array may die at once.
+constexpr int kMetaSegs = 48;
+struct PackedMetaArgs {
+  int32_t seg[kMetaSegs][5];  // row, p0, len, first packed row, first tile
+  int32_t* tiles;
+  int32_t* ctx;
+};
+
+__global__ __launch_bounds__(64) void packed_meta_kernel(PackedMetaArgs a) {
+  const int32_t* s = a.seg[blockIdx.x];
+  const int row = s[0], p0 = s[1], len = s[2], q0 = s[3], t0 = s[4];
+  for (int i = threadIdx.x; i < len; i += 64) a.ctx[q0 + i] = p0 + i + 1;
+  const int nt = (len + kPackedTile - 1) / kPackedTile;
+  for (int t = threadIdx.x; t < nt; t += 64)
+    *reinterpret_cast<int4*>(a.tiles + 4 * (size_t)(t0 + t)) =
+        int4{q0 + t * kPackedTile, min(kPackedTile, len - t * kPackedTile), row,
+             p0 + t * kPackedTile};
+}
+
+struct PackedShape {
+  int m = 0, ntile = 0, maxend = 0;
+};
+
+// Host validation of a segment list against the view's page table.
+int packed_shape(const pa_kv_view* kv, const pa_prefill_seg* segs, int nseg, PackedShape* ps) {
+  LLM_REQUIRE(kv && segs, "pa_prefill_packed: NULL argument");
+  LLM_REQUIRE(nseg >= 1, "pa_prefill_packed: need nseg >= 1");
+  LLM_REQUIRE(kv->page_size > 0 && kv->max_tiles > 0, "pa_prefill_packed: empty page table");
+  long long m = 0, ntile = 0;
+  int maxend = 0;
+  std::vector<int32_t> seen(nseg);
+  for (int j = 0; j < nseg; ++j) {
+    const pa_prefill_seg& s = segs[j];
+    LLM_REQUIRE(s.len >= 1 && s.p0 >= 0, "pa_prefill_packed: every segment needs len >= 1 and p0 >= 0");
+    LLM_REQUIRE(s.row >= 0 && s.row < kv->num_beams, "pa_prefill_packed: row outside the page table");
+    LLM_REQUIRE(((long long)s.p0 + s.len + kv->page_size - 1) / kv->page_size <= kv->max_tiles,
+                "pa_prefill_packed: positions past the page table's max_tiles");
+    seen[j] = s.row;
+    m += s.len;
+    ntile += (s.len + kPackedTile - 1) / kPackedTile;
+    maxend = std::max(maxend, s.p0 + s.len);
+  }
+  std::sort(seen.begin(), seen.end());
+  LLM_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "pa_prefill_packed: a page-table row appears in more than one segment");
+  LLM_REQUIRE(m < (1ll << 30), "pa_prefill_packed: more than 2^30 packed rows");
+  ps->m = (int)m, ps->ntile = (int)ntile, ps->maxend = maxend;
+  return LLM_OK;
+}
+
+size_t align16(size_t n) { return (n + 15) / 16 * 16; }
+
+}  // namespace
+
+size_t pa_prefill_packed_meta_bytes(int m, int ntile) {
+  return align16(((size_t)4 * ntile + m) * sizeof(int32_t));
+}
+
+size_t pa_prefill_packed_part_bytes(const pa_kv_view* kv, int maxend, int ntile, int m) {
+  if (!pa_prefill_supported(kv) || m <= 0 || ntile <= 0) return 0;
+  const PrefillPlan p = split_plan(kv, maxend, ntile, 4);
+  if (p.nsplit <= 1) return 0;
+  return (size_t)m * kv->num_heads * p.nsplit * (size_t)(kv->head_dim + 2) * sizeof(float);
+}
+
+// split_plan gives at most `want` splits whatever the key range, and nq tiles
+// hold at most 64 nq rows.
+size_t pa_prefill_packed_part_bound(const pa_kv_view* kv, int max_rows) {
+  if (!pa_prefill_supported(kv) || max_rows <= 0) return 0;
+  size_t b = 0;
+  for (int nq = 1; nq <= max_rows; ++nq) {
+    const int want = std::min(std::max(kTargetWgs / std::max(nq * kv->num_heads, 1), 1), 128);
+    const size_t rows = std::min<size_t>(max_rows, (size_t)kPackedTile * nq);
+    b = std::max(b, rows * kv->num_heads * want * (size_t)(kv->head_dim + 2) * sizeof(float));
+  }
+  return b;
+}
+
+int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                               int out_stride, const int32_t* tiles_dev, int ntile,
+                               const int32_t* ctx_dev, int m, int maxend, float sm_scale,
+                               void* part_ws, size_t part_bytes, hipStream_t st,
+                               const PaRowOutputs* rows) {
+  LLM_REQUIRE(kv && q && tiles_dev && ctx_dev, "pa_prefill_packed: NULL argument");
+  if (!pa_prefill_supported(kv))
+    return fail(LLM_ERR_UNSUPPORTED,
+                "pa_prefill_packed: fp16 or FP8 (e4m3) pools with head_dim 64 or 128 and "
+                "page_size 16 or 32 only");
+  const int H = kv->num_heads, D = kv->head_dim, hid = H * D, TS = kv->page_size;
+  LLM_REQUIRE(m >= 1 && ntile >= 1 && ntile <= m && maxend >= 1,
+              "pa_prefill_packed: need m >= 1 rows in 1 .. m tiles");
+  LLM_REQUIRE((long long)(maxend + TS - 1) / TS <= kv->max_tiles,
+              "pa_prefill_packed: positions past the page table's max_tiles");
+  if (q_stride <= 0) q_stride = hid;
+  if (out_stride <= 0) out_stride = hid;
+  LLM_REQUIRE(q_stride >= hid && out_stride >= hid && q_stride % 4 == 0 && out_stride % 4 == 0,
+              "pa_prefill_packed: row strides must be >= H*D and multiples of 4");
+  LLM_REQUIRE(reinterpret_cast<uintptr_t>(q) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(tiles_dev) % 16 == 0,
+              "pa_prefill_packed: q, out and the tile table must be 16-byte aligned");
+  const bool row_out = rows && (rows->q || rows->out16);
+  // one (nsplit, pps) for the launch: the longest segment end, every tile
+  const PrefillPlan pl = split_plan(kv, maxend, ntile, 4);
+  const size_t need = pa_prefill_packed_part_bytes(kv, maxend, ntile, m);
+  const bool split = pl.nsplit > 1 && part_ws && part_bytes >= need &&
+                     (out == nullptr || out_stride == hid) &&
+                     (!row_out || rows->pack);  // the merge writes packed o_proj inputs
+  LLM_REQUIRE(out || (split && row_out), "pa_prefill_packed: out is NULL");
+  PaPrefillArgs a{};
+  a.q = q;
+  a.q_stride = q_stride;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.k_pool = static_cast<const uint8_t*>(kv->k_pool);
+  a.v_pool = static_cast<const uint8_t*>(kv->v_pool);
+  a.page_stride = kv_view_page_stride(*kv);
+  a.tiles = tiles_dev;
+  a.page_table = kv->page_table;
+  a.H = H;
+  a.max_tiles = kv->max_tiles;
+  a.num_pages = kv->num_pages;
+  a.m = m;
+  a.qscale = sm_scale * kLog2e;
+  if (split) {
+    a.nsplit = pl.nsplit;
+    a.pps = pl.pps;
+    a.part_acc = static_cast<float*>(part_ws);
+    a.part_ml = a.part_acc + (size_t)m * H * pl.nsplit * D;
+  } else {
+    a.nsplit = 1;
+    a.pps = kv->max_tiles;
+  }
+  const float out_scale = (rows && kv->kv_dtype == LLM_FP8) ? rows->out_scale : 1.f;
+  a.out_scale = out_scale;
+  const hipError_t e = kv->kv_dtype == LLM_FP8
+                           ? launch_prefill_shape<LLM_FP8>(a, D, TS, 4, ntile, st)
+                           : launch_prefill_shape<LLM_F16>(a, D, TS, 4, ntile, st);
+  if (e != hipSuccess)
+    return fail(LLM_ERR_HIP, std::string("pa_prefill_packed launch: ") + hipGetErrorString(e));
+  if (split)  // a row's context selects the splits its own tile wrote
+    return pa_merge_rows_internal(a.part_acc, a.part_ml, (rows && !rows->keep_out) ? nullptr : out,
+                                  rows, ctx_dev, -1, m, H, D, maxend, TS, pl.pps, pl.nsplit,
+                                  kv->max_tiles, st, out_scale);
+  if (row_out) {  // one pass: convert the fp32 rows into the o_proj input
+    if (rows->q)
+      LLM_HIP_RET(launch_quantize_rows(out, m, hid, rows->q, rows->inv_scale, st, rows->pack));
+    if (rows->out16)
+      LLM_HIP_RET(launch_to_f16(out, (size_t)m * hid, rows->out16, st, rows->pack ? hid : 0));
+  }
+  return LLM_OK;
+}
+
 }  // namespace llm
+
+extern "C" int pa_prefill_packed_tiles(const pa_kv_view* kv, const pa_prefill_seg* segs, int nseg,
+                                       int32_t* tiles, int cap) {
+  llm::PackedShape ps;
+  if (llm::packed_shape(kv, segs, nseg, &ps) != LLM_OK) return -1;
+  if (!tiles || cap < ps.ntile) return ps.ntile;
+  int q0 = 0, t = 0;
+  for (int j = 0; j < nseg; ++j) {
+    for (int o = 0; o < segs[j].len; o += llm::kPackedTile, ++t) {
+      tiles[4 * t + 0] = q0 + o;
+      tiles[4 * t + 1] = std::min(llm::kPackedTile, segs[j].len - o);
+      tiles[4 * t + 2] = segs[j].row;
+      tiles[4 * t + 3] = segs[j].p0 + o;
+    }
+    q0 += segs[j].len;
+  }
+  return ps.ntile;
+}
+
+extern "C" size_t pa_prefill_packed_workspace_bytes(const pa_kv_view* kv,
+                                                    const pa_prefill_seg* segs, int nseg,
+                                                    int split) {
+  llm::PackedShape ps;
+  if (llm::packed_shape(kv, segs, nseg, &ps) != LLM_OK) return 0;
+  return llm::pa_prefill_packed_meta_bytes(ps.m, ps.ntile) +
+         (split ? llm::pa_prefill_packed_part_bytes(kv, ps.maxend, ps.ntile, ps.m) : 0);
+}
+
+extern "C" int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                                 int out_stride, const pa_prefill_seg* segs, int nseg,
+                                 float sm_scale, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  using namespace llm;
+  LLM_REQUIRE(kv && q && out, "pa_prefill_packed: NULL argument");
+  PackedShape ps;
+  const int rc = packed_shape(kv, segs, nseg, &ps);
+  if (rc) return rc;
+  if (!pa_prefill_supported(kv))
+    return fail(LLM_ERR_UNSUPPORTED,
+                "pa_prefill_packed: fp16 or FP8 (e4m3) pools with head_dim 64 or 128 and "
+                "page_size 16 or 32 only");
+  const int hid = kv->num_heads * kv->head_dim;
+  const int qs = q_stride <= 0 ? hid : q_stride, os = out_stride <= 0 ? hid : out_stride;
+  LLM_REQUIRE(qs >= hid && os >= hid && qs % 4 == 0 && os % 4 == 0,
+              "pa_prefill_packed: row strides must be >= H*D and multiples of 4");
+  LLM_REQUIRE(reinterpret_cast<uintptr_t>(q) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+              "pa_prefill_packed: q and out must be 16-byte aligned");
+  const size_t meta = pa_prefill_packed_meta_bytes(ps.m, ps.ntile);
+  LLM_REQUIRE(workspace && workspace_bytes >= meta &&
+                  reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+              "pa_prefill_packed: workspace smaller than pa_prefill_packed_workspace_bytes(.., 0) "
+              "or not 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  int32_t* tiles = static_cast<int32_t*>(workspace);
+  int32_t* ctx = tiles + (size_t)4 * ps.ntile;
+  PackedMetaArgs ma{};
+  ma.tiles = tiles;
+  ma.ctx = ctx;
+  int q0 = 0, t0 = 0;
+  for (int j0 = 0; j0 < nseg; j0 += kMetaSegs) {
+    const int n = std::min(kMetaSegs, nseg - j0);
+    for (int j = 0; j < n; ++j) {
+      const pa_prefill_seg& s = segs[j0 + j];
+      const int32_t v[5] = {s.row, s.p0, s.len, q0, t0};
+      std::copy(v, v + 5, ma.seg[j]);
+      q0 += s.len;
+      t0 += (s.len + kPackedTile - 1) / kPackedTile;
+    }
+    hipLaunchKernelGGL(packed_meta_kernel, dim3(n), dim3(64), 0, st, ma);
+    LLM_HIP_RET(hipGetLastError());
+  }
+  return pa_prefill_packed_internal(kv, q, qs, out, os, tiles, ps.ntile, ctx, ps.m, ps.maxend,
+                                    sm_scale, static_cast<uint8_t*>(workspace) + meta,
+                                    workspace_bytes - meta, st, nullptr);
+}
 
 extern "C" size_t pa_prefill_workspace_bytes(const pa_kv_view* kv, int p0, int m) {
   return llm::pa_prefill_ws_bytes(kv, p0, m);

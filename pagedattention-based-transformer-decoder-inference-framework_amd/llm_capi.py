@@ -38,6 +38,11 @@ class PaKvView(ctypes.Structure):
                 ("kv_dtype", ctypes.c_int32), ("page_stride", ctypes.c_int64)]
 
 
+class PaPrefillSeg(ctypes.Structure):
+    """pa_prefill_seg: len rows at positions p0 .. of page-table row `row`."""
+    _fields_ = [("row", ctypes.c_int32), ("p0", ctypes.c_int32), ("len", ctypes.c_int32)]
+
+
 class WeightGemmTuneArgs(ctypes.Structure):
     """weight_gemm_tune's argument (csrc/tune/gemm_tune.hip, tuning library only):
     every field of the decoder's WeightGemm and, with has_kv, of KvAppendView
@@ -113,6 +118,16 @@ _SIGS = {
     "pa_decode_ex_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pa_prefill": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p, c_int, c_int,
                            c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "pa_prefill_packed_tiles": (c_int, [ctypes.POINTER(PaKvView), ctypes.POINTER(PaPrefillSeg),
+                                        c_int, c_i32p, c_int]),
+    "pa_prefill_packed_workspace_bytes": (c_size_t, [ctypes.POINTER(PaKvView),
+                                                     ctypes.POINTER(PaPrefillSeg), c_int, c_int]),
+    "pa_prefill_packed": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p, c_int,
+                                  ctypes.POINTER(PaPrefillSeg), c_int, c_float, c_void_p,
+                                  c_size_t, c_void_p]),
+    "llm_decoder_prefill_rows": (c_int, [c_void_p, c_i32p, c_i32p, c_i32p, c_int]),
+    "llm_decoder_set_packed_prefill": (c_int, [c_void_p, c_int]),
+    "llm_decoder_packed_prefill": (c_int, [c_void_p]),
     "gemm_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gemm_pack_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "i8_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -380,6 +395,38 @@ def pa_prefill(q, k_pool, v_pool, page_table, *, row, p0, sm_scale=1.0, out=None
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=q.device) if ws_bytes else None
     check(lib.pa_prefill(ctypes.byref(view), ptr(q), q_stride, ptr(out), out.stride(0), row, p0,
                          m, sm_scale, ptr(ws), ws_bytes, stream_ptr(stream)))
+    return out
+
+
+def prefill_segs(segs):
+    """A ctypes pa_prefill_seg array of (row, p0, len) tuples."""
+    return (PaPrefillSeg * max(len(segs), 1))(*[PaPrefillSeg(*map(int, s)) for s in segs])
+
+
+def pa_prefill_packed(q, k_pool, v_pool, page_table, *, segs, sm_scale=1.0, out=None,
+                      split=True, stream=None):
+    """Causal attention of prompt chunks of several sequences in one launch
+    (pa_prefill_packed): q [m][H][D] (or a [m][stride] row view whose first
+    H*D floats are the heads), m = sum of the segment lengths, segs =
+    [(row, p0, len), ...] in packed order; returns out [m][H][D] fp32.
+    split=False gives the workspace of the one-pass form."""
+    import torch
+    lib = load()
+    m = q.shape[0]
+    H, D = page_table.shape[1], k_pool.shape[2]
+    if q.stride(-1) != 1:
+        raise ValueError("q rows must be contiguous")
+    if m != sum(int(s[2]) for s in segs):
+        raise ValueError("q rows must equal the sum of the segment lengths")
+    if out is None:
+        out = torch.empty((m, H, D), dtype=torch.float32, device=q.device)
+    view = kv_view(k_pool, v_pool, page_table)
+    arr = prefill_segs(segs)
+    ws_bytes = lib.pa_prefill_packed_workspace_bytes(ctypes.byref(view), arr, len(segs),
+                                                     1 if split else 0)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    check(lib.pa_prefill_packed(ctypes.byref(view), ptr(q), q.stride(0), ptr(out), out.stride(0),
+                                arr, len(segs), sm_scale, ptr(ws), ws_bytes, stream_ptr(stream)))
     return out
 
 
