@@ -36,6 +36,7 @@
 #include "gemm.hpp"
 #include "kv_cache_impl.hpp"
 #include "pa_decode.hpp"
+#include "prefill_pack.hpp"
 #include "row_ops.hpp"
 
 using namespace llm;
@@ -136,8 +137,7 @@ struct llm_decoder {
   float* tap_s = nullptr;
   int tap(int l, int stage, const struct Rows& R, int K, hipStream_t st);
   int layer_norm_into(WeightGemm& g, const struct Rows& R, const float* gamma, const float* beta,
-                      hipStream_t st, float* zero_x = nullptr);
-  LnSource embed_src;  // set by step_head: the next LayerNorm reads E[token] rows
+                      hipStream_t st, float* zero_x = nullptr, const LnSource* emb = nullptr);
 
   ~llm_decoder() {
     if (h_oflag) (void)hipHostFree(h_oflag);
@@ -166,7 +166,7 @@ struct llm_decoder {
   int qa_ld = 0;
   size_t b16 = 0;  // max_batch rounded up to 16-row tiles
 
-  int layer_pre(int l, hipStream_t st, const struct Rows& R);
+  int layer_pre(int l, hipStream_t st, const struct Rows& R, const LnSource* emb = nullptr);
   int layer_attn(int l, hipStream_t st, const struct Rows& R);
   int attn_request(const struct Rows& R, pa_kv_view* view, PaRequest* rq, int l = 0);
   bool quant_prologue(const struct Rows& R) const;
@@ -174,9 +174,7 @@ struct llm_decoder {
   bool wgm_quant_ok(const struct Rows& R);
   bool fc2_split(const struct Rows& R) const;
   int layer_post(int l, hipStream_t st, const struct Rows& R);
-  struct Rows step_rows(int r0, int n, uint8_t* ws);
-  int step_head(hipStream_t st, int r0, int n);
-  int step_tail(hipStream_t st, int r0, int n);
+  int decode_rows(struct Rows* R, bool scratch_oproj = false);
   int next_tokens(const float* xr, int n, int r0, const int32_t* ctr, hipStream_t st,
                   int32_t* adv_pos = nullptr, int32_t* adv_ctx = nullptr);
   int enqueue_step(hipStream_t st);
@@ -191,12 +189,18 @@ struct llm_decoder {
   size_t pws_bytes = 0;
   int pf_cap = 0;
   int prefill_reserve(int C);
+  struct PassSeg;
+  int prefill_pass(const std::vector<PassSeg>& segs, bool packed, hipStream_t st);
+  int prefill_run(const int32_t* rows, const int32_t* toks, const int32_t* lens, int nrows,
+                  long long total, bool packed, hipStream_t st);
   int prefill(int row, const int32_t* toks, int n, hipStream_t st);
   // llm_decoder_set_packed_prefill: generate / beam_search prefill all their
   // rows through prefill_rows
   bool packed_prefill = false;
   int prefill_rows(const int32_t* rows, const int32_t* toks, const int32_t* lens, int nrows,
                    hipStream_t st);
+  int prefill_prompts(const int32_t* prompts, const int32_t* prompt_lens, int prompt_stride, int n,
+                      int row_step);
 };
 
 static int check_cfg(const llm_decoder_config& c) {
@@ -460,9 +464,10 @@ extern "C" int llm_decoder_set_f16_weights(llm_decoder* d, const llm_f16_weights
 // ---------------------------------------------------------------------------
 // step
 // ---------------------------------------------------------------------------
-// The rows one layer pass works on: the decode rows (rows r0.. of the step
-// buffers, one token each) or a prefill chunk (n tokens of one sequence,
-// beam_rows[m] = its page-table row).  Every buffer is row-indexed.
+// The rows one layer pass works on: the decode rows (the active batch in the
+// step buffers, one token each; decode_rows) or a prefill pass (n prompt
+// tokens, beam_rows[m] = the page-table row of token m; prefill_pass).  Every
+// buffer is row-indexed.
 struct Rows {
   int n = 0;
   float* x = nullptr;   // [n][hid] residual-free hidden state
@@ -474,8 +479,7 @@ struct Rows {
   float* sa = nullptr;  // [n] int8 row scales
   const int32_t* pos = nullptr;  // [n] position written this pass
   const int32_t* ctx = nullptr;  // [n] context length attended (pos + 1)
-  const int32_t* beam_rows = nullptr;  // page-table row per row; NULL: table_row0 + m
-  int table_row0 = 0;
+  const int32_t* beam_rows = nullptr;  // page-table row per row; NULL: row m
   int row_group = 1;
   // INT8 rows too wide for the o_proj quantising prologue (wgm_quant_ok): the
   // attention writes fp32 rows merged in the workgroup and a quantise launch
@@ -508,20 +512,20 @@ struct Rows {
 // Activations feeding a weight GEMM (qa int8 / a16 fp16) are kept in packed-A
 // order (common.hpp a_frag_off_*): their producers (LayerNorm+quant, the
 // attention merge, the row quantiser) write MFMA A-fragments directly, so
-// every GEMM A load is one coalesced 1 KiB read.  Row offsets r0 are
-// multiples of 16, so r0 is the same base offset in both layouts (r0 * K
-// elements).
-int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R) {
+// every GEMM A load is one coalesced 1 KiB read.
+// emb (optional): the first LayerNorm reads embedding rows, not R.x (the
+// decode step's layer 0; prefill rows come from launch_embed).
+int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R, const LnSource* emb) {
   const size_t lh = (size_t)l * hid;
   pa_kv_view view;
   RET_IF(kv_cache_view(kv, l, &view));
   KvAppendView app;
   app.pos = R.pos;
-  app.page_table = view.page_table + (size_t)R.table_row0 * H * view.max_tiles;
+  app.page_table = view.page_table;
   app.rows = R.beam_rows;
   app.k_pool = kv_cache_k_pool(kv);
   app.v_pool = kv_cache_v_pool(kv);
-  app.num_beams = view.num_beams - R.table_row0;
+  app.num_beams = view.num_beams;
   app.max_tiles = view.max_tiles;
   app.page_size = TS;
   app.num_pages = view.num_pages;
@@ -541,19 +545,20 @@ int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R) {
   g.C = R.q; g.c_cols = hid; g.c_ld = hid;  // q only: K and V go straight into the pages
   g.kv = &app;
   if (wdtype == LLM_I8) g.sa = R.sa, g.sw = sw_qkv.p + (size_t)l * 3 * hid;
-  RET_IF(layer_norm_into(g, R, ln1_g.p + lh, ln1_b.p + lh, st));
+  RET_IF(layer_norm_into(g, R, ln1_g.p + lh, ln1_b.p + lh, st, nullptr, emb));
   RET_IF(weight_gemm(g, st));
   return tap(l, 0, R, hid, st);
 }
 
 // LN(x) as the GEMM's A: fused into the GEMM as its LayerNorm prologue when
 // the rows' A image fits in LDS (decode rows), else a LayerNorm (+ quant)
-// launch writing the packed A the GEMM reads.
+// launch writing the packed A the GEMM reads.  emb (optional): the rows are
+// the token embedding rows it names, not R.x; there is no embed launch in a
+// decode step (enqueue_step).
 int llm_decoder::layer_norm_into(WeightGemm& g, const Rows& R, const float* gamma,
-                                 const float* beta, hipStream_t st, float* zero_x) {
-  // the step's first LayerNorm reads the token embedding rows (step_head)
-  LnSource src = embed_src;
-  embed_src = LnSource{};
+                                 const float* beta, hipStream_t st, float* zero_x,
+                                 const LnSource* emb) {
+  LnSource src = emb ? *emb : LnSource{};
   src.zero_x = zero_x;  // (the LayerNorm launch only: the caller checks fc2_split)
   if (!R.is_prefill() && ln_fusable(wdtype, R.n, hid)) {
     g.ln_x = R.x; g.ln_g = gamma; g.ln_b = beta; g.ln_eps = 1e-5f;
@@ -639,8 +644,6 @@ bool llm_decoder::fc2_split(const Rows& R) const {
 // the rows' page-table rows and what the launch is to return (pa_plan.hpp).
 int llm_decoder::attn_request(const Rows& R, pa_kv_view* view, PaRequest* rq, int l) {
   RET_IF(kv_cache_view(kv, l, view));
-  view->page_table += (size_t)R.table_row0 * H * view->max_tiles;  // rows r0..
-  view->num_beams -= R.table_row0;
   // the split merge also produces the o_proj input (packed int8 + scale, or fp16)
   const PaOut out = quant_prologue(R) || R.wgm_quant ? PaOut::F32_ROWS  // quantised by the o_proj
                     : wdtype == LLM_I8               ? PaOut::ROW_Q     // prologue or layer_attn
@@ -656,30 +659,10 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
   pa_kv_view view;
   PaRequest rq;
   RET_IF(attn_request(R, &view, &rq, l));
-  if (R.is_prefill() && pa_prefill_supported(&view)) {
-    // one MFMA pass over the chunk (K/V pages read once per 32 queries), then
-    // the o_proj input conversion the decode merge would have fused
-    PaRowOutputs ro;
-    ro.pack = 1;
-    ro.keep_out = 0;
-    if (wdtype == LLM_I8) {
-      ro.q = static_cast<int8_t*>(R.act);
-      ro.inv_scale = R.sa;
-    } else {
-      ro.out16 = R.act;
-    }
-    // LLM_FP8 pages: the scales enter as in the decode launch below
-    ro.out_scale = v_scale[l];
-    const float sm = kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale;
-    if (R.prefill_ntile > 0)
-      return pa_prefill_packed_internal(&view, R.q, hid, R.o, hid, R.prefill_tiles,
-                                        R.prefill_ntile, R.ctx, R.n, R.prefill_maxend, sm,
-                                        R.attn_ws, R.attn_ws_bytes, st, &ro);
-    return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n, sm,
-                               R.attn_ws, R.attn_ws_bytes, st, &ro);
-  }
-  // the request's pointers; the fp32 rows (R.o) are only needed by a
-  // single-split (direct) launch, and are the output of F32_ROWS
+  // the request's pointers: the o_proj input (packed) that the launch writes
+  // besides, or in place of, the fp32 rows (R.o: only needed by a single-split
+  // direct launch, and the output of F32_ROWS).  A prefill pass asks for
+  // ROW_Q or ROW_F16 (attn_request: none of the fused decode forms).
   PaRowOutputs ro;
   ro.pack = 1;
   ro.keep_out = 0;
@@ -700,9 +683,19 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
   // LLM_FP8 pages: K's scale folded into the score multiplier, V's applied to
   // the normalised heads by the launch (1 and 1 for fp16 pages)
   ro.out_scale = v_scale[l];
-  RET_IF(pa_decode_internal(&view, rq, R.q, hid, R.o, R.beam_rows, R.ctx,
-                            kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale,
-                            R.attn_ws, R.attn_ws_bytes, st, &ro));
+  const float sm = kvt == LLM_FP8 ? cfg.attn_scale * k_scale[l] : cfg.attn_scale;
+  if (R.is_prefill() && pa_prefill_supported(&view)) {
+    // one MFMA pass over the chunk (K/V pages read once per 32 queries), then
+    // the o_proj input conversion the decode merge would have fused
+    if (R.prefill_ntile > 0)
+      return pa_prefill_packed_internal(&view, R.q, hid, R.o, hid, R.prefill_tiles,
+                                        R.prefill_ntile, R.ctx, R.n, R.prefill_maxend, sm,
+                                        R.attn_ws, R.attn_ws_bytes, st, &ro);
+    return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n, sm,
+                               R.attn_ws, R.attn_ws_bytes, st, &ro);
+  }
+  RET_IF(pa_decode_internal(&view, rq, R.q, hid, R.o, R.beam_rows, R.ctx, sm, R.attn_ws,
+                            R.attn_ws_bytes, st, &ro));
   if (R.wgm_quant)  // the packed int8 o_proj input + row scales
     LLM_HIP_RET(launch_quantize_rows(R.o, R.n, hid, static_cast<int8_t*>(R.act), R.sa, st, 1));
   return LLM_OK;
@@ -760,24 +753,40 @@ int llm_decoder::layer_post(int l, hipStream_t st, const Rows& R) {
   return weight_gemm(g, st);
 }
 
-// Rows r0 .. r0 + n - 1 of the decode-step buffers.
-Rows llm_decoder::step_rows(int r0, int n, uint8_t* ws) {
-  Rows R;
-  R.n = n;
-  R.x = x.p + (size_t)r0 * hid;
-  R.q = qkv.p + (size_t)r0 * hid;
-  R.o = o.p + (size_t)r0 * hid;
-  R.h1 = h1.p + (size_t)r0 * inter;
-  R.act = wdtype == LLM_I8 ? (void*)(qa.p + (size_t)r0 * qa_ld) : (void*)(a16.p + (size_t)r0 * qa_ld);
-  if (wdtype == LLM_F16) R.act2 = a16.p + (b16 + (size_t)r0) * qa_ld;
-  R.sa = sa.p + r0;
-  R.pos = pos.p + r0;
-  R.ctx = ctx.p + r0;
-  R.table_row0 = r0;
-  R.row_group = r0 % row_group == 0 ? row_group : 1;
-  R.attn_ws = ws;
+// The decode rows: the active batch in the step buffers, with the forms of
+// its launches decided (the fused o_proj, the workgroup merge + quantise) --
+// what the step enqueues, what llm_decoder_attention_plan reports and what
+// llm_decoder_run_attention times.
+// scratch_oproj (run_attention): the fused o_proj writes the attention rows'
+// fp32 buffer, not x, and accumulates into columns of its own (oacc_run:
+// allocated on first use, zero, and every completed column clears itself, as
+// the step's do) with a range flag of its own (oflag_run: a clamp there never
+// fails a step or a sync).
+int llm_decoder::decode_rows(Rows* out, bool scratch_oproj) {
+  Rows& R = *out = Rows{};
+  R.n = batch;
+  R.x = x.p; R.q = qkv.p; R.o = o.p; R.h1 = h1.p;
+  R.act = wdtype == LLM_I8 ? (void*)qa.p : (void*)a16.p;
+  if (wdtype == LLM_F16) R.act2 = a16.p + b16 * qa_ld;
+  R.sa = sa.p;
+  R.pos = pos.p;
+  R.ctx = ctx.p;
+  R.row_group = row_group;
+  R.attn_ws = attn_ws.p;
   R.attn_ws_bytes = attn_ws_bytes;
-  return R;
+  if (oproj_fusable(R)) {
+    if (scratch_oproj && !oacc_run.p) {
+      RET_IF(oacc_run.alloc(oacc.n));
+      LLM_HIP_RET(hipMemset(oacc_run.p, 0, sizeof(long long) * oacc_run.n));
+      RET_IF(oflag_run.alloc(1));
+      LLM_HIP_RET(hipMemset(oflag_run.p, 0, sizeof(int)));
+    }
+    R.oacc = scratch_oproj ? oacc_run.p : oacc.p;
+    R.oproj_out = scratch_oproj ? R.o : R.x;
+    R.oflag = scratch_oproj ? oflag_run.p : oflag.p;
+  }
+  R.wgm_quant = wgm_quant_ok(R);
+  return LLM_OK;
 }
 
 // Tap stage `stage` of layer l (0: LN1 out, 1: attention out, 2: LN2 out,
@@ -791,12 +800,11 @@ int llm_decoder::tap(int l, int stage, const Rows& R, int K, hipStream_t st) {
   const size_t es = f16 ? 2 : 1;
   const size_t slot = (size_t)l * 4 + stage;
   const size_t n16 = ((size_t)R.n + 15) / 16 * 16;
-  const size_t r0 = (size_t)R.table_row0;  // rows r0.. of the step (16-row aligned)
   const void* src = f16 && stage == 3 ? R.act2 : R.act;
-  LLM_HIP_RET(hipMemcpyAsync(tap_q + (slot * b16 * qa_ld + r0 * K) * es, src, n16 * K * es,
+  LLM_HIP_RET(hipMemcpyAsync(tap_q + slot * b16 * qa_ld * es, src, n16 * K * es,
                              hipMemcpyDeviceToDevice, st));
   if (!f16)
-    LLM_HIP_RET(hipMemcpyAsync(tap_s + slot * maxB + r0, R.sa, sizeof(float) * R.n,
+    LLM_HIP_RET(hipMemcpyAsync(tap_s + slot * maxB, R.sa, sizeof(float) * R.n,
                                hipMemcpyDeviceToDevice, st));
   return LLM_OK;
 }
@@ -832,34 +840,22 @@ int llm_decoder::next_tokens(const float* xr, int n, int r0, const int32_t* ctr,
   return LLM_OK;
 }
 
-// The step's embedding: no launch of its own; layer 0's first LayerNorm
-// (launch or GEMM prologue) reads E[token] rows directly (embed_src).
-int llm_decoder::step_head(hipStream_t st, int r0, int n) {
-  (void)st;
-  embed_src = LnSource{};
-  embed_src.emb = reinterpret_cast<const _Float16*>(emb.p);
-  embed_src.tok = tokens.p + r0;
-  embed_src.V = V;
-  (void)n;
-  return LLM_OK;
-}
-
-int llm_decoder::step_tail(hipStream_t st, int r0, int n) {
-  return next_tokens(x.p + (size_t)r0 * hid, n, r0, pos.p + r0, st, pos.p + r0, ctx.p + r0);
-}
-
-// One decode step of all active rows (captured into the step graph).
+// One decode step of all active rows (captured into the step graph).  The
+// embedding has no launch of its own: layer 0's first LayerNorm (launch or
+// GEMM prologue) reads E[token] rows directly.
 int llm_decoder::enqueue_step(hipStream_t st) {
-  Rows R = step_rows(0, batch, attn_ws.p);
-  if (oproj_fusable(R)) R.oacc = oacc.p, R.oproj_out = R.x, R.oflag = oflag.p;
-  R.wgm_quant = wgm_quant_ok(R);
-  RET_IF(step_head(st, 0, batch));
+  Rows R;
+  RET_IF(decode_rows(&R));
+  LnSource embed;
+  embed.emb = reinterpret_cast<const _Float16*>(emb.p);
+  embed.tok = tokens.p;
+  embed.V = V;
   for (int l = 0; l < L; ++l) {
-    RET_IF(layer_pre(l, st, R));
+    RET_IF(layer_pre(l, st, R, l == 0 ? &embed : nullptr));
     RET_IF(layer_attn(l, st, R));
     RET_IF(layer_post(l, st, R));
   }
-  return step_tail(st, 0, batch);
+  return next_tokens(x.p, batch, 0, pos.p, st, pos.p, ctx.p);
 }
 
 int llm_decoder::run_step(const int32_t* tokens_host, float* logits_dev, int32_t* next_host,
@@ -983,185 +979,179 @@ int llm_decoder::prefill_reserve(int C) {
   return LLM_OK;
 }
 
-// Chunked prefill of `n` prompt tokens of active row `row` (the reference's
-// is_prefill pass, attention/attention_cuda.hpp:21): the chunk's tokens are
-// the rows of one layer pass — M = chunk-size weight GEMMs, the K/V of every
-// token appended to the row's pages by the qkv epilogue, and causal attention
-// through the same paged decode kernel (token i of the chunk attends to the
-// row's positions < p0 + i + 1 via beam_ids = row, context_lens = p0 + i + 1).
-// The last token's logits pick the row's next token (argmax / sampling), so
-// decode steps continue from the prompt.
+// A segment of a prefill pass: len prompt tokens (toks) at positions p0 .. of
+// active row `row`; last: the row's prompt ends with it.
+struct llm_decoder::PassSeg {
+  int row, p0, len;
+  const int32_t* toks;
+  bool last;
+};
+
+// One layer pass over the tokens of `segs` (the reference's is_prefill pass,
+// attention/attention_cuda.hpp:21): the tokens are the rows of the pass —
+// M = pass-size weight GEMMs, the K/V of every token appended to its row's
+// pages by the qkv epilogue, and causal attention.  Everything in the pass is
+// row-wise (pmeta carries each packed row's position, context, page-table row
+// and token: through the paged decode kernel, token i of a segment attends to
+// its row's positions < p0 + i + 1 via beam_ids = row, context_lens = p0 + i
+// + 1) except the MFMA attention: `packed` takes the pass's tile table
+// (pa_prefill_packed), else the pass is one segment and takes the
+// single-sequence launch (pa_prefill; no tile table is built or uploaded).
+// A row whose last token is in the pass gets its next token from that packed
+// row's logits (argmax / sampling), so decode steps continue from the prompt.
+int llm_decoder::prefill_pass(const std::vector<PassSeg>& segs, bool packed, hipStream_t st) {
+  const int CAP = pf_cap;  // pmeta's array stride
+  const int nseg = (int)segs.size();
+  std::vector<int32_t> meta((size_t)(packed ? 8 : 4) * CAP), pc((size_t)2 * nseg);
+  int m = 0, maxend = 0, ntile = 0;
+  for (const PassSeg& s : segs) {
+    LLM_REQUIRE(m + s.len <= CAP && (packed || nseg == 1), "prefill: bad pass");
+    for (int i = 0; i < s.len; ++i) {
+      meta[m + i] = s.p0 + i;
+      meta[CAP + m + i] = s.p0 + i + 1;
+      meta[2 * CAP + m + i] = s.row;
+      meta[3 * CAP + m + i] = s.toks[i];
+    }
+    m += s.len;
+    maxend = std::max(maxend, s.p0 + s.len);
+  }
+  if (packed) {
+    pa_kv_view v0;
+    RET_IF(kv_cache_view(kv, 0, &v0));
+    std::vector<pa_prefill_seg> tsegs;
+    for (const PassSeg& s : segs) tsegs.push_back(pa_prefill_seg{s.row, s.p0, s.len});
+    ntile = pa_prefill_packed_tiles(&v0, tsegs.data(), nseg, meta.data() + 4 * CAP, CAP);
+    LLM_REQUIRE(ntile >= 1 && ntile <= CAP, "prefill_rows: bad segment list");
+  }
+  {
+    KvCache* k = kv_impl(kv);
+    std::lock_guard<std::mutex> gk(k->mu);
+    for (const PassSeg& s : segs)
+      for (int t = s.p0; t < s.p0 + s.len; t = (t / TS + 1) * TS) RET_IF(k->prepare_append(s.row, t));
+    RET_IF(k->sync(st));
+  }
+  LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), ((size_t)4 * CAP + 4 * ntile) * sizeof(int32_t),
+                             hipMemcpyHostToDevice, st));
+  Rows R;
+  R.n = m;
+  R.x = px.p; R.q = pq.p; R.o = po.p; R.h1 = ph1.p; R.act = pact.p; R.sa = psa.p;
+  if (wdtype == LLM_F16)
+    R.act2 = pact.p + (((size_t)CAP + 15) / 16 * 16) * std::max(hid, inter) * 2;
+  R.pos = pmeta.p; R.ctx = pmeta.p + CAP; R.beam_rows = pmeta.p + 2 * CAP;
+  if (packed) {
+    R.prefill_tiles = pmeta.p + 4 * CAP;
+    R.prefill_ntile = ntile;
+    R.prefill_maxend = maxend;
+  } else {
+    R.prefill_row = segs[0].row;
+    R.prefill_p0 = segs[0].p0;
+  }
+  R.attn_ws = pws.p; R.attn_ws_bytes = pws_bytes;
+  LLM_HIP_RET(launch_embed(emb.p, pmeta.p + 3 * CAP, m, hid, V, px.p, st));
+  for (int l = 0; l < L; ++l) {
+    RET_IF(layer_pre(l, st, R));
+    RET_IF(layer_attn(l, st, R));
+    RET_IF(layer_post(l, st, R));
+  }
+  int q0 = 0;
+  for (int j = 0; j < nseg; ++j) {
+    const PassSeg& s = segs[j];
+    const int last = q0 + s.len - 1;
+    h_pos[s.row] = s.p0 + s.len;
+    if (s.last) {  // the row's last token: logits -> its next token, decode state
+      RET_IF(next_tokens(px.p + (size_t)last * hid, 1, s.row, pmeta.p + last, st));
+      pc[2 * j] = s.p0 + s.len;
+      pc[2 * j + 1] = s.p0 + s.len + 1;
+      LLM_HIP_RET(hipMemcpyAsync(pos.p + s.row, &pc[2 * j], sizeof(int32_t),
+                                 hipMemcpyHostToDevice, st));
+      LLM_HIP_RET(hipMemcpyAsync(ctx.p + s.row, &pc[2 * j + 1], sizeof(int32_t),
+                                 hipMemcpyHostToDevice, st));
+    }
+    q0 += s.len;
+  }
+  LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc are this pass's staging
+  return LLM_OK;
+}
+
+// The prompts of `nrows` active rows (lens[i] tokens of row rows[i], `total`
+// > 0 in all, concatenated in toks; checked by the caller) through layer
+// passes of up to kPrefillChunk tokens, packed by prefill_passes
+// (prefill_pack.hpp): segments of different rows share a pass, and a long
+// prompt continues in the next pass.
+int llm_decoder::prefill_run(const int32_t* rows, const int32_t* toks, const int32_t* lens,
+                             int nrows, long long total, bool packed, hipStream_t st) {
+  const int C = (int)std::min<long long>(total, kPrefillChunk);
+  RET_IF(prefill_reserve(C));
+  std::vector<int> start(nrows);
+  std::vector<const int32_t*> row_toks(nrows);
+  for (int i = 0; i < nrows; ++i) {
+    start[i] = h_pos[rows[i]];
+    row_toks[i] = toks;
+    toks += lens[i];
+  }
+  std::vector<PassSeg> segs;
+  for (const PrefillPass& pass : prefill_passes(start.data(), lens, nrows, C)) {
+    segs.clear();
+    for (const PrefillSeg& s : pass) {
+      const int off = s.p0 - start[s.src];
+      segs.push_back(PassSeg{rows[s.src], s.p0, s.len, row_toks[s.src] + off,
+                             off + s.len == lens[s.src]});
+    }
+    RET_IF(prefill_pass(segs, packed, st));
+  }
+  return LLM_OK;
+}
+
+// Chunked prefill of `n` prompt tokens of active row `row` (llm_decoder_prefill):
+// one segment per pass, attended by the single-sequence launch.
 int llm_decoder::prefill(int row, const int32_t* toks, int n, hipStream_t st) {
   LLM_REQUIRE(weights_ready, "prefill: weights not loaded");
   LLM_REQUIRE(row >= 0 && row < batch, "prefill: row is not active");
   LLM_REQUIRE(n >= 1 && toks, "prefill: need >= 1 token");
   LLM_REQUIRE(h_pos[row] + n < cfg.max_seq_len, "prefill: prompt exceeds max_seq_len");
   for (int i = 0; i < n; ++i) LLM_REQUIRE(toks[i] >= 0 && toks[i] < V, "prefill: token id out of range");
-  const int C = std::min(n, kPrefillChunk);
-  RET_IF(prefill_reserve(C));
-  KvCache* k = kv_impl(kv);
-  std::vector<int32_t> meta((size_t)4 * C), pc(2);
-  for (int c0 = 0; c0 < n; c0 += C) {
-    const int m = std::min(C, n - c0);
-    const int p0 = h_pos[row];
-    {
-      std::lock_guard<std::mutex> gk(k->mu);
-      for (int t = p0; t < p0 + m; t = (t / TS + 1) * TS) RET_IF(k->prepare_append(row, t));
-      RET_IF(k->sync(st));
-    }
-    for (int i = 0; i < m; ++i) {
-      meta[i] = p0 + i;
-      meta[C + i] = p0 + i + 1;
-      meta[2 * C + i] = row;
-      meta[3 * C + i] = toks[c0 + i];
-    }
-    LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), meta.size() * sizeof(int32_t),
-                               hipMemcpyHostToDevice, st));
-    Rows R;
-    R.n = m;
-    R.x = px.p; R.q = pq.p; R.o = po.p; R.h1 = ph1.p; R.act = pact.p; R.sa = psa.p;
-    if (wdtype == LLM_F16)
-      R.act2 = pact.p + (((size_t)C + 15) / 16 * 16) * std::max(hid, inter) * 2;
-    R.pos = pmeta.p; R.ctx = pmeta.p + C; R.beam_rows = pmeta.p + 2 * C;
-    R.prefill_row = row;
-    R.prefill_p0 = p0;
-    R.attn_ws = pws.p; R.attn_ws_bytes = pws_bytes;
-    LLM_HIP_RET(launch_embed(emb.p, pmeta.p + 3 * C, m, hid, V, px.p, st));
-    embed_src = LnSource{};  // (a failed step enqueue could have left it set)
-    for (int l = 0; l < L; ++l) {
-      RET_IF(layer_pre(l, st, R));
-      RET_IF(layer_attn(l, st, R));
-      RET_IF(layer_post(l, st, R));
-    }
-    h_pos[row] = p0 + m;
-    if (c0 + m == n) {  // last token: logits -> the row's next token, decode state
-      RET_IF(next_tokens(px.p + (size_t)(m - 1) * hid, 1, row, pmeta.p + (m - 1), st));
-      pc[0] = p0 + m;
-      pc[1] = p0 + m + 1;
-      LLM_HIP_RET(hipMemcpyAsync(pos.p + row, &pc[0], sizeof(int32_t), hipMemcpyHostToDevice, st));
-      LLM_HIP_RET(hipMemcpyAsync(ctx.p + row, &pc[1], sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc staging reused next chunk
-  }
-  return LLM_OK;
+  return prefill_run(&row, toks, &n, 1, n, false, st);
 }
 
 // Packed prefill (llm_decoder_prefill_rows): the prompts of several active rows
-// through shared layer passes.  A pass is up to kPrefillChunk packed tokens,
-// filled greedily in row order -- segments (row, p0, len) of different rows, a
-// long prompt continuing in the next pass at its new position, so a row is in
-// a pass at most once.  Everything in a layer pass is row-wise (pmeta carries
-// each packed row's position, context, page-table row and token) except the
-// MFMA attention, which takes the pass's tile table (pa_prefill_packed); rows
-// whose last token is in the pass get their next token from that packed row.
+// through shared layer passes, attended by the tile-table launch (also where
+// a pass holds one segment: the two launches plan their splits differently).
 int llm_decoder::prefill_rows(const int32_t* rows, const int32_t* toks, const int32_t* lens,
                               int nrows, hipStream_t st) {
   LLM_REQUIRE(weights_ready, "prefill_rows: weights not loaded");
   LLM_REQUIRE(nrows >= 0 && (nrows == 0 || (rows && lens)), "prefill_rows: NULL argument");
   long long total = 0;
-  {
-    std::vector<char> seen(batch, 0);
-    for (int i = 0; i < nrows; ++i) {
-      LLM_REQUIRE(rows[i] >= 0 && rows[i] < batch, "prefill_rows: row is not active");
-      LLM_REQUIRE(!seen[rows[i]], "prefill_rows: a row is given twice");
-      seen[rows[i]] = 1;
-      LLM_REQUIRE(lens[i] >= 0, "prefill_rows: negative length");
-      LLM_REQUIRE((long long)h_pos[rows[i]] + lens[i] < cfg.max_seq_len,
-                  "prefill_rows: prompt exceeds max_seq_len");
-      total += lens[i];
-    }
-    LLM_REQUIRE(total == 0 || toks, "prefill_rows: tokens is NULL");
-    for (long long i = 0; i < total; ++i)
-      LLM_REQUIRE(toks[i] >= 0 && toks[i] < V, "prefill_rows: token id out of range");
+  std::vector<char> seen(batch, 0);
+  for (int i = 0; i < nrows; ++i) {
+    LLM_REQUIRE(rows[i] >= 0 && rows[i] < batch, "prefill_rows: row is not active");
+    LLM_REQUIRE(!seen[rows[i]], "prefill_rows: a row is given twice");
+    seen[rows[i]] = 1;
+    LLM_REQUIRE(lens[i] >= 0, "prefill_rows: negative length");
+    LLM_REQUIRE((long long)h_pos[rows[i]] + lens[i] < cfg.max_seq_len,
+                "prefill_rows: prompt exceeds max_seq_len");
+    total += lens[i];
   }
+  LLM_REQUIRE(total == 0 || toks, "prefill_rows: tokens is NULL");
+  for (long long i = 0; i < total; ++i)
+    LLM_REQUIRE(toks[i] >= 0 && toks[i] < V, "prefill_rows: token id out of range");
   if (total == 0) return LLM_OK;
-  const int C = (int)std::min<long long>(total, kPrefillChunk);
-  RET_IF(prefill_reserve(C));
-  const int CAP = pf_cap;  // pmeta's array stride
-  pa_kv_view v0;
-  RET_IF(kv_cache_view(kv, 0, &v0));
-  KvCache* k = kv_impl(kv);
-  std::vector<int32_t> meta((size_t)8 * CAP), pc((size_t)2 * nrows);
-  std::vector<pa_prefill_seg> segs;
-  std::vector<int> seg_src;  // index into rows / lens of each segment
-  int ri = 0;                // the row being packed, `done` of its tokens placed
-  int done = 0;
-  long long tok0 = 0;        // its first token in toks
-  while (ri < nrows) {
-    segs.clear();
-    seg_src.clear();
-    int m = 0, maxend = 0;
-    while (ri < nrows && m < C) {
-      const int left = lens[ri] - done;
-      if (left == 0) {
-        tok0 += lens[ri];
-        ++ri, done = 0;
-        continue;
-      }
-      const int len = std::min(left, C - m), row = rows[ri], p0 = h_pos[row];
-      for (int i = 0; i < len; ++i) {
-        meta[m + i] = p0 + i;
-        meta[CAP + m + i] = p0 + i + 1;
-        meta[2 * CAP + m + i] = row;
-        meta[3 * CAP + m + i] = toks[tok0 + done + i];
-      }
-      segs.push_back(pa_prefill_seg{row, p0, len});
-      seg_src.push_back(ri);
-      m += len;
-      maxend = std::max(maxend, p0 + len);
-      done += len;
-      if (done < lens[ri]) break;  // the pass is full; the row continues in the next
-      tok0 += lens[ri];
-      ++ri, done = 0;
-    }
-    if (m == 0) break;
-    const int nseg = (int)segs.size();
-    const int ntile = pa_prefill_packed_tiles(&v0, segs.data(), nseg, meta.data() + 4 * CAP, CAP);
-    LLM_REQUIRE(ntile >= 1 && ntile <= CAP, "prefill_rows: bad segment list");
-    {
-      std::lock_guard<std::mutex> gk(k->mu);
-      for (const pa_prefill_seg& s : segs)
-        for (int t = s.p0; t < s.p0 + s.len; t = (t / TS + 1) * TS) RET_IF(k->prepare_append(s.row, t));
-      RET_IF(k->sync(st));
-    }
-    LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), ((size_t)4 * CAP + 4 * ntile) * sizeof(int32_t),
-                               hipMemcpyHostToDevice, st));
-    Rows R;
-    R.n = m;
-    R.x = px.p; R.q = pq.p; R.o = po.p; R.h1 = ph1.p; R.act = pact.p; R.sa = psa.p;
-    if (wdtype == LLM_F16)
-      R.act2 = pact.p + (((size_t)CAP + 15) / 16 * 16) * std::max(hid, inter) * 2;
-    R.pos = pmeta.p; R.ctx = pmeta.p + CAP; R.beam_rows = pmeta.p + 2 * CAP;
-    R.prefill_tiles = pmeta.p + 4 * CAP;
-    R.prefill_ntile = ntile;
-    R.prefill_maxend = maxend;
-    R.attn_ws = pws.p; R.attn_ws_bytes = pws_bytes;
-    LLM_HIP_RET(launch_embed(emb.p, pmeta.p + 3 * CAP, m, hid, V, px.p, st));
-    embed_src = LnSource{};  // (a failed step enqueue could have left it set)
-    for (int l = 0; l < L; ++l) {
-      RET_IF(layer_pre(l, st, R));
-      RET_IF(layer_attn(l, st, R));
-      RET_IF(layer_post(l, st, R));
-    }
-    int q0 = 0;
-    for (int j = 0; j < nseg; ++j) {
-      const pa_prefill_seg& s = segs[j];
-      const int src = seg_src[j], last = q0 + s.len - 1;
-      h_pos[s.row] = s.p0 + s.len;
-      // the row's last token: logits -> its next token, decode state
-      if (src < ri) {
-        RET_IF(next_tokens(px.p + (size_t)last * hid, 1, s.row, pmeta.p + last, st));
-        pc[2 * src] = s.p0 + s.len;
-        pc[2 * src + 1] = s.p0 + s.len + 1;
-        LLM_HIP_RET(hipMemcpyAsync(pos.p + s.row, &pc[2 * src], sizeof(int32_t),
-                                   hipMemcpyHostToDevice, st));
-        LLM_HIP_RET(hipMemcpyAsync(ctx.p + s.row, &pc[2 * src + 1], sizeof(int32_t),
-                                   hipMemcpyHostToDevice, st));
-      }
-      q0 += s.len;
-    }
-    LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc staging reused next pass
+  return prefill_run(rows, toks, lens, nrows, total, true, st);
+}
+
+// prompt[:-1] of n sequences into rows s * row_step (generate: every row;
+// beam search: beam 0 of every sequence), through shared passes
+// (packed_prefill) or row by row.  The prefill's own token choice is not used.
+int llm_decoder::prefill_prompts(const int32_t* prompts, const int32_t* prompt_lens,
+                                 int prompt_stride, int n, int row_step) {
+  std::vector<int32_t> prow(n), plen(n), ptok;
+  for (int s = 0; s < n; ++s) {
+    const int32_t* ps = prompts + (size_t)s * prompt_stride;
+    prow[s] = s * row_step;
+    plen[s] = prompt_lens[s] - 1;
+    if (packed_prefill) ptok.insert(ptok.end(), ps, ps + plen[s]);
+    else if (plen[s] > 0) RET_IF(prefill(prow[s], ps, plen[s], stream));
   }
+  if (packed_prefill) return prefill_rows(prow.data(), ptok.data(), plen.data(), n, stream);
   return LLM_OK;
 }
 
@@ -1184,6 +1174,27 @@ static int reset_rows(llm_decoder* d, int batch, int start_pos) {
   return LLM_OK;
 }
 
+// Non-contiguous page gather (shuffled page pool, seed 7).
+static void shuffle_free_pages(KvCache* k, uint64_t seed) {
+  std::lock_guard<std::mutex> gk(k->mu);
+  std::mt19937_64 rng(seed ^ 7);
+  for (auto& f : k->free_lists) std::shuffle(f.begin(), f.end(), rng);
+}
+
+// The reserved page tables pushed, then seeded random K/V over the whole
+// pools (K scaled so q.k ~ O(1)); LLM_FP8 pools hold the same values encoded
+// at scale 1.
+static int fill_pools(llm_decoder* d, uint64_t seed) {
+  KvCache* k = kv_impl(d->kv);
+  RET_IF(kv_cache_sync(d->kv, d->stream));
+  const size_t np = (size_t)k->num_pages, pe = k->page_elems, ps = k->page_stride() / k->es;
+  const auto fill = d->kvt == LLM_FP8 ? launch_fill_random_fp8 : launch_fill_random_f16;
+  LLM_HIP_RET(fill(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
+  LLM_HIP_RET(fill(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  return LLM_OK;
+}
+
 extern "C" int llm_decoder_begin_synthetic(llm_decoder* d, int batch, int context_len,
                                            uint64_t seed, int shuffle) {
   LLM_REQUIRE(d, "llm_decoder_begin_synthetic: NULL");
@@ -1192,24 +1203,9 @@ extern "C" int llm_decoder_begin_synthetic(llm_decoder* d, int batch, int contex
               "llm_decoder_begin_synthetic: context_len must be in [0, max_seq_len)");
   LLM_HIP_RET(hipStreamSynchronize(d->stream));
   RET_IF(reset_rows(d, batch, context_len));
-  KvCache* k = kv_impl(d->kv);
-  {
-    std::lock_guard<std::mutex> gk(k->mu);
-    if (shuffle) {  // non-contiguous page gather (shuffled page pool, seed 7)
-      std::mt19937_64 rng(seed ^ 7);
-      for (auto& f : k->free_lists) std::shuffle(f.begin(), f.end(), rng);
-    }
-  }
+  if (shuffle) shuffle_free_pages(kv_impl(d->kv), seed);
   for (int b = 0; b < batch; ++b) RET_IF(kv_cache_reserve(d->kv, b, context_len));
-  RET_IF(kv_cache_sync(d->kv, d->stream));
-  // seeded random K/V over the whole pools (K scaled so q.k ~ O(1)); LLM_FP8
-  // pools hold the same values encoded at scale 1
-  const size_t np = (size_t)k->num_pages, pe = k->page_elems, ps = k->page_stride() / k->es;
-  const auto fill = d->kvt == LLM_FP8 ? launch_fill_random_fp8 : launch_fill_random_f16;
-  LLM_HIP_RET(fill(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
-  LLM_HIP_RET(fill(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
-  LLM_HIP_RET(hipStreamSynchronize(d->stream));
-  return LLM_OK;
+  return fill_pools(d, seed);
 }
 
 extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_width,
@@ -1225,12 +1221,7 @@ extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_wi
   LLM_HIP_RET(hipStreamSynchronize(d->stream));
   const int batch = num_seqs * beam_width;
   RET_IF(reset_rows(d, batch, ctx_len));
-  KvCache* k = kv_impl(d->kv);
-  if (shuffle) {
-    std::lock_guard<std::mutex> gk(k->mu);
-    std::mt19937_64 rng(seed ^ 7);
-    for (auto& f : k->free_lists) std::shuffle(f.begin(), f.end(), rng);
-  }
+  if (shuffle) shuffle_free_pages(kv_impl(d->kv), seed);
   // beam 0 of each sequence owns the shared prefix; the other beams fork its
   // page table (shared pages, refcounted) and then get private pages for their
   // own beam_len tokens.
@@ -1240,12 +1231,7 @@ extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_wi
     for (int w = 1; w < beam_width; ++w) RET_IF(kv_cache_fork(d->kv, b0, b0 + w));
     for (int w = 0; w < beam_width; ++w) RET_IF(kv_cache_reserve(d->kv, b0 + w, ctx_len));
   }
-  RET_IF(kv_cache_sync(d->kv, d->stream));
-  const size_t np = (size_t)k->num_pages, pe = k->page_elems, ps = k->page_stride() / k->es;
-  const auto fill = d->kvt == LLM_FP8 ? launch_fill_random_fp8 : launch_fill_random_f16;
-  LLM_HIP_RET(fill(k->k_pool, np, pe, ps, seed * 2 + 1, 0.05f, d->stream));
-  LLM_HIP_RET(fill(k->v_pool, np, pe, ps, seed * 2 + 2, 1.0f, d->stream));
-  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  RET_IF(fill_pools(d, seed));
   d->row_group = beam_width;
   d->graph_batch = -1;  // re-capture: the attention launch depends on row_group
   return LLM_OK;
@@ -1306,9 +1292,8 @@ extern "C" int llm_decoder_attention_plan(llm_decoder* d, int* nsplit, int* form
   LLM_REQUIRE(d && nsplit && form, "llm_decoder_attention_plan: NULL");
   std::lock_guard<std::mutex> g(d->mu);
   LLM_REQUIRE(d->batch > 0, "llm_decoder_attention_plan: no active rows");
-  Rows R = d->step_rows(0, d->batch, d->attn_ws.p);
-  if (d->oproj_fusable(R)) R.oacc = d->oacc.p, R.oproj_out = R.x, R.oflag = d->oflag.p;
-  R.wgm_quant = d->wgm_quant_ok(R);
+  Rows R;
+  RET_IF(d->decode_rows(&R));
   pa_kv_view view;
   PaRequest rq;
   PaLaunch p;
@@ -1326,21 +1311,8 @@ extern "C" int llm_decoder_run_attention(llm_decoder* d, int layer, void* stream
   LLM_REQUIRE(d->batch > 0, "llm_decoder_run_attention: no active rows");
   LLM_REQUIRE(layer >= 0 && layer < d->L, "llm_decoder_run_attention: layer out of range");
   hipStream_t st = stream ? as_stream(stream) : d->stream;
-  Rows R = d->step_rows(0, d->batch, d->attn_ws.p);
-  // the step's fused o_proj writes the attention rows' fp32 buffer here, not
-  // x, and accumulates into columns of its own (oacc_run: zero at allocation,
-  // and every completed column clears itself, as the step's do) with a range
-  // flag of its own (oflag_run: a clamp here never fails a step or a sync)
-  if (d->oproj_fusable(R)) {
-    if (!d->oacc_run.p) {
-      RET_IF(d->oacc_run.alloc(d->oacc.n));
-      LLM_HIP_RET(hipMemset(d->oacc_run.p, 0, sizeof(long long) * d->oacc_run.n));
-      RET_IF(d->oflag_run.alloc(1));
-      LLM_HIP_RET(hipMemset(d->oflag_run.p, 0, sizeof(int)));
-    }
-    R.oacc = d->oacc_run.p, R.oproj_out = R.o, R.oflag = d->oflag_run.p;
-  }
-  R.wgm_quant = d->wgm_quant_ok(R);
+  Rows R;
+  RET_IF(d->decode_rows(&R, true));  // (a timed run: its own o_proj target)
   return d->layer_attn(layer, st, R);
 }
 
@@ -1393,6 +1365,23 @@ extern "C" int llm_decoder_context_len(const llm_decoder* d, int row) {
   return d->h_pos[row];
 }
 
+// The prompts of generate / beam_search (`who`): every one 1 .. prompt_stride
+// tokens of the vocabulary.  *max_len: the longest.
+static int check_prompts(const std::string& who, const llm_decoder* d, const int32_t* prompts,
+                         const int32_t* prompt_lens, int prompt_stride, int n, int* max_len) {
+  *max_len = 0;
+  for (int s = 0; s < n; ++s) {
+    LLM_REQUIRE(prompt_lens[s] >= 1 && prompt_lens[s] <= prompt_stride,
+                who + ": every prompt needs >= 1 token");
+    for (int i = 0; i < prompt_lens[s]; ++i) {
+      const int t = prompts[(size_t)s * prompt_stride + i];
+      LLM_REQUIRE(t >= 0 && t < d->V, who + ": token id out of range");
+    }
+    *max_len = std::max(*max_len, prompt_lens[s]);
+  }
+  return LLM_OK;
+}
+
 extern "C" int llm_decoder_generate(llm_decoder* d, const int32_t* prompts,
                                     const int32_t* prompt_lens, int prompt_stride, int batch,
                                     int max_gen_len, float temperature, int32_t* out) {
@@ -1418,15 +1407,8 @@ extern "C" int llm_decoder_generate(llm_decoder* d, const int32_t* prompts,
   } sampling_guard(d);
   LLM_REQUIRE(batch >= 1 && batch <= d->maxB, "llm_decoder_generate: batch out of range");
   int max_len = 0;
-  for (int b = 0; b < batch; ++b) {
-    LLM_REQUIRE(prompt_lens[b] >= 1 && prompt_lens[b] <= prompt_stride,
-                "llm_decoder_generate: every prompt needs >= 1 token");
-    for (int i = 0; i < prompt_lens[b]; ++i) {
-      const int t = prompts[(size_t)b * prompt_stride + i];
-      LLM_REQUIRE(t >= 0 && t < d->V, "llm_decoder_generate: token id out of range");
-    }
-    max_len = std::max(max_len, prompt_lens[b]);
-  }
+  RET_IF(check_prompts("llm_decoder_generate", d, prompts, prompt_lens, prompt_stride, batch,
+                       &max_len));
   if (max_gen_len == 0) return LLM_OK;
   LLM_REQUIRE(max_len + max_gen_len - 1 <= d->cfg.max_seq_len,
               "llm_decoder_generate: prompt + max_gen_len exceeds max_seq_len");
@@ -1434,20 +1416,7 @@ extern "C" int llm_decoder_generate(llm_decoder* d, const int32_t* prompts,
   RET_IF(reset_rows(d, batch, 0));
   // every prompt but its last token goes through chunked prefill; decode steps
   // then run all rows in lockstep, each at its own position
-  if (d->packed_prefill) {  // ... all rows through shared passes
-    std::vector<int32_t> prow(batch), plen(batch), ptok;
-    for (int b = 0; b < batch; ++b) {
-      prow[b] = b;
-      plen[b] = prompt_lens[b] - 1;
-      const int32_t* pb = prompts + (size_t)b * prompt_stride;
-      ptok.insert(ptok.end(), pb, pb + plen[b]);
-    }
-    RET_IF(d->prefill_rows(prow.data(), ptok.data(), plen.data(), batch, d->stream));
-  } else {
-    for (int b = 0; b < batch; ++b)
-      if (prompt_lens[b] > 1)
-        RET_IF(d->prefill(b, prompts + (size_t)b * prompt_stride, prompt_lens[b] - 1, d->stream));
-  }
+  RET_IF(d->prefill_prompts(prompts, prompt_lens, prompt_stride, batch, 1));
   // a step whose fused o_proj clamped (LLM_ERR_RANGE) still produced its ids:
   // generation runs to the end, fills `out`, and then returns the status
   std::vector<int32_t> tok(batch), next(batch);
@@ -1503,15 +1472,8 @@ extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
   LLM_REQUIRE(d->V >= 2 * W, "llm_decoder_beam_search: vocab_size < 2 * beam_width");
   LLM_REQUIRE(d->V <= 65536, "llm_decoder_beam_search: vocab_size > 65536");
   int max_len = 0;
-  for (int s = 0; s < num_seqs; ++s) {
-    LLM_REQUIRE(prompt_lens[s] >= 1 && prompt_lens[s] <= prompt_stride,
-                "llm_decoder_beam_search: every prompt needs >= 1 token");
-    for (int i = 0; i < prompt_lens[s]; ++i) {
-      const int t = prompts[(size_t)s * prompt_stride + i];
-      LLM_REQUIRE(t >= 0 && t < d->V, "llm_decoder_beam_search: token id out of range");
-    }
-    max_len = std::max(max_len, prompt_lens[s]);
-  }
+  RET_IF(check_prompts("llm_decoder_beam_search", d, prompts, prompt_lens, prompt_stride, num_seqs,
+                       &max_len));
   LLM_REQUIRE(max_len + max_new - 1 <= d->cfg.max_seq_len,
               "llm_decoder_beam_search: prompt + max_new_tokens exceeds max_seq_len");
   std::lock_guard<std::mutex> g(d->mu);
@@ -1529,20 +1491,9 @@ extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
   RET_IF(reset_rows(d, rows, 0));
   // prompt[:-1] into beam 0's pages (the prefill's own token choice, argmax or
   // a draw, is not used), shared with the other beams
-  if (d->packed_prefill) {  // every sequence's beam 0 through shared passes
-    std::vector<int32_t> prow(num_seqs), plen(num_seqs), ptok;
-    for (int s = 0; s < num_seqs; ++s) {
-      prow[s] = s * W;
-      plen[s] = prompt_lens[s] - 1;
-      const int32_t* pb = prompts + (size_t)s * prompt_stride;
-      ptok.insert(ptok.end(), pb, pb + plen[s]);
-    }
-    RET_IF(d->prefill_rows(prow.data(), ptok.data(), plen.data(), num_seqs, d->stream));
-  }
+  RET_IF(d->prefill_prompts(prompts, prompt_lens, prompt_stride, num_seqs, W));
   for (int s = 0; s < num_seqs; ++s) {
     const int b0 = s * W, n = prompt_lens[s] - 1;
-    if (n > 0 && !d->packed_prefill)
-      RET_IF(d->prefill(b0, prompts + (size_t)s * prompt_stride, n, d->stream));
     for (int w = 1; w < W; ++w) {
       if (n > 0) RET_IF(kv_cache_fork(d->kv, b0, b0 + w));
       d->h_pos[b0 + w] = n;

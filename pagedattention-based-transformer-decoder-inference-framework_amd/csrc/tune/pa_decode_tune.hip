@@ -6,10 +6,12 @@
 // routes a beam-group launch to the experiment switched on), the pa_decode_tune
 // A/B entry of the split kernel's register-stage / cache-policy variants
 // (scripts/bench_kernels.py, scripts/tune_attention.py; each variant is the
-// PaSplitCfg fields it changes) and pa_plan_tune, the planner's test entry.
+// PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry, and
+// prefill_passes_tune, the prefill pass packer's.
 #include "tune/pa_decode_tune.hpp"
 #include "tune/pa_beam_steal.hpp"
 #include "pa_tuning.hpp"
+#include "prefill_pack.hpp"
 
 namespace llm {
 
@@ -1023,6 +1025,30 @@ extern "C" int pa_plan_tune(int B, int H, int D, int T, int page_size, int max_t
   *nsplit = p.nsplit;
   *form = p.form();
   return LLM_OK;
+}
+
+// Tuning hook: the prefill pass packer (prefill_pack.hpp) on explicit rows
+// (start[i], len[i]), so a test reads the pass structure the decoder runs.
+// out: (pass, row index, p0, len) per segment, the first `capacity` of them;
+// returns the segment count (which may exceed capacity), -1 on bad arguments.
+extern "C" int prefill_passes_tune(const int32_t* start, const int32_t* len, int nrows, int cap,
+                                   int32_t* out, int capacity) {
+  if (nrows < 0 || cap < 1 || capacity < 0 || (nrows && (!start || !len)) || (capacity && !out))
+    return -1;
+  for (int i = 0; i < nrows; ++i)
+    if (start[i] < 0 || len[i] < 0) return -1;
+  int n = 0, pi = 0;
+  for (const PrefillPass& pass : prefill_passes(start, len, nrows, cap)) {
+    for (const PrefillSeg& s : pass) {
+      if (n < capacity) {
+        int32_t* q = out + 4 * (size_t)n;
+        q[0] = pi, q[1] = s.src, q[2] = s.p0, q[3] = s.len;
+      }
+      ++n;
+    }
+    ++pi;
+  }
+  return n;
 }
 
 // Tuning hook (not part of include/llm_decoder.h): run the split kernel of

@@ -105,6 +105,8 @@ _SIGS = {
                                c_i32p, c_i32p]),
     # tuning library only: the launch planner on explicit request fields
     "pa_plan_tune": (c_int, [c_int] * 11 + [c_ll] * 3 + [c_i32p, c_i32p]),
+    # tuning library only: the prefill pass packer (csrc/prefill_pack.hpp)
+    "prefill_passes_tune": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_int]),
     "pa_decode": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_void_p,
                           c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
                           c_void_p]),
