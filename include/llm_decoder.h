@@ -335,6 +335,26 @@ int beam_select_rows(const float* logits, const float* score_in, int num_seqs, i
  * seed ^ (row << 32) ^ counter, top 24 bits / 2^24. */
 float sample_uniform_host(uint64_t seed, int row, int counter);
 
+/* The standard rotary table (layout of attention/attention_kernel_utils.cuh:20-35,
+ * table[t * head_dim + d] = cos, [.. + d + 1] = sin for even d): for pair
+ * i = d / 2, angle = t * theta^(-2 i / head_dim), computed in double and
+ * rounded to fp32.  Host only.  theta > 0, head_dim even and > 0,
+ * num_pos >= 1, table float [num_pos][head_dim]. */
+int llm_rope_table(double theta, int head_dim, int num_pos, float* table);
+
+/* Rotary embedding in place (the per-position interleaved rotation of
+ * attention/attention_kernel_utils.cuh:20-35) of x fp32 [rows][H][D], row r at
+ * x + r * x_stride (x_stride >= H * D floats), by position pos[r]: with
+ * c = table[pos[r] * D + d], s = table[pos[r] * D + d + 1] for even d,
+ *   x'[d] = x[d] c - x[d+1] s,   x'[d+1] = x[d] s + x[d+1] c,
+ * every product rounded to fp32 on its own, then one add (no fma).  A row
+ * whose position is outside [0, num_pos) is left as it is and the table is not
+ * read for it.  For callers of pa_decode / pa_prefill who project q and K
+ * themselves; the decoder's qkv projection applies the same rotation in its
+ * epilogue (llm_decoder_set_rope).  D even; table device float [num_pos][D]. */
+int rope_rows(float* x, int x_stride, const int32_t* pos, int rows, int H, int D,
+              const float* table, int num_pos, void* stream);
+
 /* Per-row dynamic int8 quantisation (attention_cpu/int8_quant.cpp:5-13,59-64):
  * scale_r = 127/(absmax_r + 1e-6); q = clamp(round(x*scale_r)); inv_scale[r] = 1/scale_r. */
 int quantize_rows(const float* x, int rows, int cols, int8_t* q, float* inv_scale, void* stream);
@@ -492,6 +512,22 @@ int llm_decoder_create_kv(const llm_decoder_config* cfg, int kv_dtype, llm_decod
 int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale, const float* v_scale);
 /* LLM_F16 or LLM_FP8. */
 int llm_decoder_kv_dtype(const llm_decoder* d);
+/* Rotary position embedding of the decoder (the per-position interleaved
+ * rotation of attention/attention_kernel_utils.cuh:20-35, see rope_rows):
+ * table is a host array [max_seq_len][head_dim] in llm_rope_table's layout,
+ * copied to the device; NULL turns rotation off (the default).  The qkv
+ * projection then rotates q and K by each row's position in its epilogue,
+ * before q is stored and before K is rounded into the pages (fp16 or e4m3,
+ * after the multiplication by 1 / k_scale); V is not rotated.  Decode steps,
+ * prompt chunks and packed prefill passes alike.  Allowed only while no rows
+ * are active, else LLM_ERR_INVALID; LLM_ERR_INVALID too for an odd head_dim
+ * or a non-finite entry.  The table is stored in no file: a KV snapshot
+ * written with rotation on holds rotated K and must be loaded into a decoder
+ * with the same table. */
+int llm_decoder_set_rope(llm_decoder* d, const float* table);
+/* 1: a rotary table is set, 0: none, -1 for NULL
+ * (attention/attention_kernel_utils.cuh:20-35). */
+int llm_decoder_rope(const llm_decoder* d);
 /* The attention kernel prompt chunks (llm_decoder_prefill, the prompts of
  * llm_decoder_generate) of this decoder's pools take: LLM_PREFILL_MFMA
  * (pa_prefill: fp16 or LLM_FP8 pools, head_dim 64 or 128, page_size 16 or 32)

@@ -372,6 +372,27 @@ class Decoder {
     check(llm_decoder_set_kv_scales(d_, k.is_none() ? nullptr : ks.data(),
                                     v.is_none() ? nullptr : vs.data()));
   }
+  // llm_decoder_set_rope: set_rope(theta=10000.0) builds the standard table
+  // (llm_rope_table), set_rope(table=ndarray) takes float32 [max_seq_len,
+  // head_dim] of (cos, sin) pairs, set_rope(None) turns rotation off
+  void set_rope(py::object table, double theta) {
+    if (table.is_none()) {
+      check(llm_decoder_set_rope(d_, nullptr));
+      return;
+    }
+    const size_t S = (size_t)cfg_.max_seq_len, D = (size_t)cfg_.head_dim;
+    if (table.is(py::ellipsis())) {
+      std::vector<float> t(S * D);
+      check(llm_rope_table(theta, cfg_.head_dim, cfg_.max_seq_len, t.data()));
+      check(llm_decoder_set_rope(d_, t.data()));
+      return;
+    }
+    auto a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(table);
+    if (!a || a.ndim() != 2 || (size_t)a.shape(0) != S || (size_t)a.shape(1) != D)
+      throw std::invalid_argument("set_rope: table must be float32 [max_seq_len, head_dim]");
+    check(llm_decoder_set_rope(d_, a.data()));
+  }
+  bool rope() const { return llm_decoder_rope(d_) == 1; }
   std::string kv_dtype() const {
     return llm_decoder_kv_dtype(d_) == LLM_FP8 ? "float8_e4m3fn" : "float16";
   }
@@ -614,6 +635,9 @@ PYBIND11_MODULE(llm_decoder, m) {
              py::arg("stream") = 0)
         .def("set_kv_scales", &Decoder::set_kv_scales, py::arg("k_scale") = py::none(),
              py::arg("v_scale") = py::none())
+        .def("set_rope", &Decoder::set_rope, py::arg("table") = py::ellipsis(),
+             py::arg("theta") = 10000.0)
+        .def_property_readonly("rope", &Decoder::rope)
         .def_property_readonly("kv_dtype", &Decoder::kv_dtype)
         .def_property_readonly("prefill_kernel", &Decoder::prefill_kernel)
         .def_property_readonly("kv_handle", &Decoder::kv_handle);
@@ -749,6 +773,15 @@ PYBIND11_MODULE(llm_decoder, m) {
         py::arg("A"), py::arg("B"), py::arg("C"), py::arg("BATCH"), py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("scaleA"), py::arg("scaleB"), py::arg("scaleC") = 1.0f,
         py::arg("bias") = 0, py::arg("activation") = "", py::arg("stream") = 0);
+  // llm_rope_table: float32 [num_pos, head_dim] of (cos, sin) pairs
+  m.def("rope_table",
+        [](double theta, int head_dim, int num_pos) {
+          if (head_dim <= 0 || num_pos <= 0) throw std::invalid_argument("rope_table: bad shape");
+          py::array_t<float> a({(py::ssize_t)num_pos, (py::ssize_t)head_dim});
+          check(llm_rope_table(theta, head_dim, num_pos, a.mutable_data()));
+          return a;
+        },
+        py::arg("theta"), py::arg("head_dim"), py::arg("num_pos"));
   m.def("workspace_bytes", &pa_decode_workspace_bytes, py::arg("B"), py::arg("H"), py::arg("D"),
         py::arg("max_tiles"), py::arg("pages_per_split") = 0);
   m.def("filter_workspace_bytes", &pa_decode_ex_workspace_bytes, py::arg("B"), py::arg("H"),

@@ -95,6 +95,12 @@ struct llm_decoder {
   kv_cache* kv = nullptr;
   int kvt = LLM_F16;
   std::vector<float> k_scale, v_scale;
+  // rotary table [max_seq_len][D] (llm_decoder_set_rope; device copy, kept
+  // once allocated): the qkv projection's epilogue rotates q and K by it
+  // (layer_pre).  Like the scales it is a kernel argument of the step graph
+  // and is stored in no file.
+  DevBuf<float> rope;
+  bool rope_on = false;
 
   // activations / state
   DevBuf<float> x, qkv, o, h1, logits, sa;
@@ -330,6 +336,28 @@ extern "C" int llm_decoder_set_kv_scales(llm_decoder* d, const float* k_scale,
   return LLM_OK;
 }
 
+// attention/attention_kernel_utils.cuh:20-35 (the rotation), see rope_rows
+extern "C" int llm_decoder_set_rope(llm_decoder* d, const float* table) {
+  LLM_REQUIRE(d, "llm_decoder_set_rope: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_rope: rows are active (set the table before "
+                             "begin_* / generate / prefill)");
+  if (table) {
+    LLM_REQUIRE(d->D % 2 == 0, "llm_decoder_set_rope: head_dim must be even");
+    const size_t n = (size_t)d->cfg.max_seq_len * d->D;
+    for (size_t i = 0; i < n; ++i)
+      LLM_REQUIRE(std::isfinite(table[i]), "llm_decoder_set_rope: every entry must be finite");
+    LLM_HIP_RET(hipStreamSynchronize(d->stream));  // nothing in flight reads the old table
+    if (!d->rope.p) RET_IF(d->rope.alloc(n));
+    LLM_HIP_RET(hipMemcpy(d->rope.p, table, n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  d->rope_on = table != nullptr;
+  d->graph_batch = -1;  // the step graph carries the table as a kernel argument
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_rope(const llm_decoder* d) { return d ? (d->rope_on ? 1 : 0) : -1; }
+
 extern "C" void llm_decoder_destroy(llm_decoder* d) {
   if (!d) return;
   if (d->stream) (void)hipStreamSynchronize(d->stream);
@@ -535,6 +563,10 @@ int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R, const LnSource*
   app.kv_dtype = kvt;
   app.k_inv_scale = 1.0f / k_scale[l];
   app.v_inv_scale = 1.0f / v_scale[l];
+  if (rope_on) {  // decode rows, prompt chunks and packed passes alike: R.pos is per row
+    app.rope = rope.p;
+    app.rope_len = cfg.max_seq_len;
+  }
   WeightGemm g;
   g.dtype = wdtype;
   g.a_packed = 1;

@@ -152,7 +152,10 @@ int llm::weight_gemm(const WeightGemm& g, hipStream_t st) {
                     static_cast<_Float16*>(kv.v_pool), kv.num_beams, kv.max_tiles, kv.page_size,
                     kv.num_pages, kv.H, kv.D,
                     kv.page_stride > 0 ? kv.page_stride : (size_t)kv.page_size * kv.D,
-                    kv.kv_dtype == LLM_FP8 ? 1 : 0, kv.k_inv_scale, kv.v_inv_scale};
+                    kv.kv_dtype == LLM_FP8 ? 1 : 0, kv.k_inv_scale, kv.v_inv_scale,
+                    kv.rope, kv.rope ? kv.rope_len : 0};
+    LLM_REQUIRE(!kv.rope || (kv.D % 2 == 0 && kv.rope_len >= 0 && g.act == LLM_ACT_NONE),
+                "weight_gemm: rotary table needs an even head_dim and no activation");
   }
   const hipError_t e = g.dtype == LLM_I8 ? launch_gemm<GemmKind::I8>(a, st)
                                          : launch_gemm<GemmKind::F16>(a, st);

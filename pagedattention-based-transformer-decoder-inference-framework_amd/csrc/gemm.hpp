@@ -23,6 +23,10 @@ struct KvAppendView {
   // layer's inverse scales (1 / k_scale, 1 / v_scale, computed on the host)
   int kv_dtype = LLM_F16;
   float k_inv_scale = 1.f, v_inv_scale = 1.f;
+  // rotary table, device float [rope_len][D] of (cos, sin) pairs per position
+  // (attention/attention_kernel_utils.cuh:20-35); NULL: q and K are not rotated
+  const float* rope = nullptr;
+  int rope_len = 0;
 };
 
 // One decode weight GEMM (decoder-internal form of i8_gemm / f16_gemm):

@@ -40,6 +40,14 @@ namespace llm {
 // instead of a separate append launch.  fp8: the pools hold LLM_FP8 bytes
 // (csrc/fp8.hpp), written as cvt_e4m3(clamp(y * k_inv / v_inv)), one byte
 // store per element; page_stride counts elements of the pools' type.
+// rope (optional): float [rope_len][D] of (cos, sin) pairs per position, the
+// reference's rotary table (attention/attention_kernel_utils.cuh:22-23).  The q
+// and K columns of row m are rotated by position pos[m] in the epilogue
+// (gemm_kernel<..., ROPE = 1>), pair (d, d + 1) for even d:
+//   x'[d] = x[d] c - x[d+1] s,  x'[d+1] = x[d] s + x[d+1] c
+// (two rounded products, one add: not contracted), before q's fp32 store and
+// K's fp16 / e4m3 conversion.  V is not rotated; a position outside
+// [0, rope_len) is left unrotated and the table is not read for it.
 struct KvAppend {
   const int32_t* pos;
   const int32_t* page_table;  // [num_beams][H][max_tiles] of this layer (row offset applied)
@@ -50,6 +58,8 @@ struct KvAppend {
   size_t page_stride;  // elements from page p to page p + 1
   int fp8;             // pools of LLM_FP8 bytes (else fp16)
   float k_inv, v_inv;  // fp8: 1 / k_scale, 1 / v_scale of the layer
+  const float* rope;   // NULL: no rotation
+  int rope_len;
 };
 
 struct GemmArgs {
@@ -252,7 +262,8 @@ __device__ __forceinline__ void seam_wait(unsigned* ctr, int n) {
   __syncthreads();
 }
 
-template <GemmKind KIND, int MT, int NT, int WAVES, int DIAG = 0, int PRO = 0, int SEAM = 0>
+template <GemmKind KIND, int MT, int NT, int WAVES, int DIAG = 0, int PRO = 0, int SEAM = 0,
+          int ROPE = 0>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int bz, int nz,
                                           int gx) {
   using Tr = GemmTraits<KIND>;
@@ -400,6 +411,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
   const int hid = kv.H * kv.D;
   float e_scale[EPT], e_bias[EPT];
   int e_pos[EPT], e_br[EPT], e_page[EPT];
+  // ROPE: (cos, sin) of the output's pair at its row's position; the q columns
+  // need pos[m] too
+  float e_cos[ROPE ? EPT : 1], e_sin[ROPE ? EPT : 1];
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
     const int o = threadIdx.x + e * NTHR;
@@ -413,7 +427,8 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
     }
     e_bias[e] = valid && a.bias && (!a.ksplit2 || bz == 0) ? a.bias[n] : 0.f;
     const bool kvcol = valid && kv.k_pool && n >= hid;
-    e_pos[e] = kvcol ? kv.pos[m] : -1;
+    const bool poscol = ROPE ? valid && kv.k_pool : kvcol;
+    e_pos[e] = poscol ? kv.pos[m] : -1;
     e_br[e] = kvcol ? (kv.rows ? kv.rows[m] : m) : -1;
   }
 
@@ -478,6 +493,14 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
         if (page >= kv.num_pages) page = -1;
       }
       e_page[e] = page;
+      if constexpr (ROPE != 0) {
+        // q and K columns at a position the table covers (n < N and m < M
+        // where p >= 0); hid = H D, so n % D is the index within the head
+        const bool rot = n < 2 * hid && p >= 0 && p < kv.rope_len;
+        const float* cs = kv.rope + (size_t)(rot ? p : 0) * kv.D + ((n % kv.D) & ~1);
+        e_cos[e] = rot ? cs[0] : 1.f;
+        e_sin[e] = rot ? cs[1] : 0.f;
+      }
     }
     while (ks < ks1) {
       if (ks + kUnroll < ks1) {
@@ -554,6 +577,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
       y = a.bias ? s + e_bias[e] : s;
     }
     y = apply_act(y, a.act);
+    if constexpr (ROPE != 0) {
+      // The pair (d, d ^ 1) sits in lanes l, l ^ 1 at this e (COLS and NTHR are
+      // even) and shares m and every skip above, so both lanes are active here
+      const float yp = mov_dpp<0xB1>(y);  // quad_perm [1,0,3,2]
+      const int p = e_pos[e];
+      if (n < 2 * hid && p >= 0 && p < kv.rope_len) {
+        const float own = y * e_cos[e], oth = yp * e_sin[e];
+        y = (n & 1) ? oth + own : own - oth;
+      }
+    }
     if (a.C && n < a.c_cols) a.C[(size_t)m * a.c_ld + n] = y;
     if (a.c16) a.c16[a_frag_off_f16(m, n, a.N >> 5)] = (_Float16)y;
     if (e_page[e] >= 0) {
@@ -572,7 +605,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
   if (stamp && lane == 0) stamp[32 + w] = phase_clock();  // [32, 48): wave end
 }
 
-template <GemmKind KIND, int MT, int NT, int WAVES, int DIAG = 0, int PRO = 0>
+template <GemmKind KIND, int MT, int NT, int WAVES, int DIAG = 0, int PRO = 0, int ROPE = 0>
 __global__ __launch_bounds__(WAVES * 64) void gemm_kernel(GemmArgs a) {
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
 #if LLM_TUNING
@@ -586,7 +619,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_kernel(GemmArgs a) {
     by = tile / (int)gridDim.x;
   }
 #endif
-  gemm_tile<KIND, MT, NT, WAVES, DIAG, PRO>(a, bx, by, bz, (int)gridDim.z, (int)gridDim.x);
+  gemm_tile<KIND, MT, NT, WAVES, DIAG, PRO, 0, ROPE>(a, bx, by, bz, (int)gridDim.z,
+                                                     (int)gridDim.x);
 }
 
 // Repack W [K][N] (row-major) into per-(16-col tile, k-step) 1 KiB blocks,
@@ -647,25 +681,37 @@ struct GemmForm {
   int prologue;  // the LayerNorm / quantising prologue kernel (PRO = 1)
 };
 
-template <GemmKind KIND, int MT, int NT>
-hipError_t launch_gemm_nt(const GemmArgs& a, const GemmForm& f, int mblocks, hipStream_t st) {
-  const int ntiles = (a.N + 15) / 16;
-  const dim3 grid((ntiles + NT - 1) / NT, mblocks, f.kslices);
+// ROPE = 1: the rotary epilogue, a kernel of its own, so that every launch
+// without a table runs the code it ran before there was one.
+template <GemmKind KIND, int MT, int NT, int ROPE>
+hipError_t launch_gemm_form(const GemmArgs& a, const GemmForm& f, dim3 grid, hipStream_t st) {
   if constexpr (NT <= 2) {
     if (f.prologue) {
       const size_t lds = ln_lds_bytes<KIND, MT, NT, 8>(a.K);
-      hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 1>), grid, dim3(512), lds, st, a);
+      hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 1, ROPE>), grid, dim3(512), lds, st, a);
       return hipGetLastError();
     }
   }
   if constexpr (MT * NT * 8 <= 64) {
     if (f.waves == 8) {
-      hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8>), grid, dim3(512), 0, st, a);
+      hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 0, ROPE>), grid, dim3(512), 0, st, a);
       return hipGetLastError();
     }
   }
-  hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 4>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 4, 0, 0, ROPE>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
+}
+
+template <GemmKind KIND, int MT, int NT>
+hipError_t launch_gemm_nt(const GemmArgs& a, const GemmForm& f, int mblocks, hipStream_t st) {
+  const int ntiles = (a.N + 15) / 16;
+  const dim3 grid((ntiles + NT - 1) / NT, mblocks, f.kslices);
+  if (a.kv.rope) {
+    // (3 / 4 column tiles, tuning build: no rotary form)
+    if constexpr (NT <= 2) return launch_gemm_form<KIND, MT, NT, 1>(a, f, grid, st);
+    return hipErrorInvalidValue;
+  }
+  return launch_gemm_form<KIND, MT, NT, 0>(a, f, grid, st);
 }
 
 template <GemmKind KIND, int MT>

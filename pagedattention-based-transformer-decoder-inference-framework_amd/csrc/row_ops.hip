@@ -1,6 +1,8 @@
 // Row-wise decoder glue kernels: LayerNorm (+ fused int8 quantisation),
 // per-row int8 quantisation, embedding gather, KV append into pages, argmax.
 // All are one workgroup per row, vectorised 16 B per lane where the row allows.
+#include <cmath>
+
 #include "common.hpp"
 #include "fp8.hpp"
 #include "gemm.hpp"
@@ -385,6 +387,30 @@ __global__ void fill_random_kernel(T* __restrict__ p, size_t n, size_t page_elem
   }
 }
 
+// Rotary embedding in place, one thread per pair (row r, head h, pair i):
+// the per-position interleaved rotation of attention/attention_kernel_utils.cuh:20-35
+// on the table's (cos, sin) at [pos[r]][2 i], the rotation the qkv
+// projection's epilogue applies (gemm_impl.hpp, ROPE): two rounded products
+// and one add per output, not contracted.  Rows at a position outside
+// [0, num_pos) are left as they are; the table is not read for them.
+__global__ __launch_bounds__(kRowThreads) void rope_rows_kernel(
+    float* __restrict__ x, size_t x_stride, const int32_t* __restrict__ pos, size_t total, int hd2,
+    int D, const float* __restrict__ table, int num_pos) {
+#pragma clang fp contract(off)  // each product rounded on its own, as the GEMM epilogue
+  const size_t i = (size_t)blockIdx.x * kRowThreads + threadIdx.x;
+  if (i >= total) return;
+  const size_t r = i / hd2;
+  const int j = (int)(i % hd2);  // pair j of the row: elements 2 j, 2 j + 1
+  const int p = pos[r];
+  if (p < 0 || p >= num_pos) return;
+  const float* cs = table + (size_t)p * D + (2 * j) % D;
+  const float c = cs[0], s = cs[1];
+  float* xp = x + r * x_stride + 2 * j;
+  const float x0 = xp[0], x1 = xp[1];
+  xp[0] = x0 * c - x1 * s;
+  xp[1] = x0 * s + x1 * c;
+}
+
 // ---------------------------------------------------------------------------
 // host launchers (internal)
 // ---------------------------------------------------------------------------
@@ -537,5 +563,38 @@ extern "C" int argmax_rows(const float* logits, int rows, int V, int32_t* out, v
   if (rows == 0) return LLM_OK;
   LLM_REQUIRE(logits && out, "argmax_rows: NULL pointer");
   LLM_HIP_RET(launch_argmax(logits, rows, V, out, nullptr, 0, as_stream(stream)));
+  return LLM_OK;
+}
+
+extern "C" int llm_rope_table(double theta, int head_dim, int num_pos, float* table) {
+  LLM_REQUIRE(table, "llm_rope_table: NULL table");
+  LLM_REQUIRE(theta > 0.0 && std::isfinite(theta), "llm_rope_table: theta must be finite and > 0");
+  LLM_REQUIRE(head_dim > 0 && head_dim % 2 == 0, "llm_rope_table: head_dim must be even and > 0");
+  LLM_REQUIRE(num_pos >= 1, "llm_rope_table: num_pos must be >= 1");
+  for (int i = 0; i < head_dim / 2; ++i) {
+    const double freq = std::pow(theta, -2.0 * (double)i / (double)head_dim);
+    for (int t = 0; t < num_pos; ++t) {
+      const double ang = (double)t * freq;
+      table[(size_t)t * head_dim + 2 * i] = (float)std::cos(ang);
+      table[(size_t)t * head_dim + 2 * i + 1] = (float)std::sin(ang);
+    }
+  }
+  return LLM_OK;
+}
+
+extern "C" int rope_rows(float* x, int x_stride, const int32_t* pos, int rows, int H, int D,
+                         const float* table, int num_pos, void* stream) {
+  LLM_REQUIRE(rows >= 0 && H > 0 && D > 0 && num_pos >= 0, "rope_rows: bad shape");
+  LLM_REQUIRE(D % 2 == 0, "rope_rows: head_dim must be even");
+  LLM_REQUIRE((long long)x_stride >= (long long)H * D, "rope_rows: x_stride < H * D");
+  if (rows == 0) return LLM_OK;
+  LLM_REQUIRE(x && pos && table, "rope_rows: NULL pointer");
+  const int hd2 = H * D / 2;
+  const size_t total = (size_t)rows * hd2;
+  LLM_REQUIRE((total + kRowThreads - 1) / kRowThreads < (1ull << 31), "rope_rows: too many rows");
+  hipLaunchKernelGGL(rope_rows_kernel, dim3((unsigned)((total + kRowThreads - 1) / kRowThreads)),
+                     dim3(kRowThreads), 0, as_stream(stream), x, (size_t)x_stride, pos, total, hd2,
+                     D, table, num_pos);
+  LLM_HIP_RET(hipGetLastError());
   return LLM_OK;
 }

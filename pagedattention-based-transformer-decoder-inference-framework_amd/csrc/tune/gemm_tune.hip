@@ -235,10 +235,13 @@ struct WeightGemmTuneArgs {
   long long kv_page_stride;
   int kv_dtype;
   float kv_k_inv_scale, kv_v_inv_scale;
+  const float* kv_rope;  // KvAppendView::rope / rope_len (appended: zero = off)
+  int kv_rope_len;
 };
 
 extern "C" int weight_gemm_tune(const WeightGemmTuneArgs* t, void* stream) {
   LLM_REQUIRE(t, "weight_gemm_tune: NULL arguments");
+  LLM_REQUIRE(t->has_kv || !t->kv_rope, "weight_gemm: rotary table without a kv append");
   KvAppendView kv;
   kv.pos = t->kv_pos;
   kv.page_table = t->kv_page_table;
@@ -251,6 +254,7 @@ extern "C" int weight_gemm_tune(const WeightGemmTuneArgs* t, void* stream) {
   kv.page_stride = (size_t)t->kv_page_stride;
   kv.kv_dtype = t->kv_dtype;
   kv.k_inv_scale = t->kv_k_inv_scale; kv.v_inv_scale = t->kv_v_inv_scale;
+  kv.rope = t->kv_rope; kv.rope_len = t->kv_rope_len;
   WeightGemm g;
   g.dtype = t->dtype;
   g.A = t->A; g.lda = t->lda; g.a_packed = t->a_packed;

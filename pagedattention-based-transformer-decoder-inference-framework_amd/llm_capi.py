@@ -60,7 +60,8 @@ class WeightGemmTuneArgs(ctypes.Structure):
                 ("kv_k_pool", c_void_p), ("kv_v_pool", c_void_p), ("kv_num_beams", c_int),
                 ("kv_max_tiles", c_int), ("kv_page_size", c_int), ("kv_num_pages", c_int),
                 ("kv_H", c_int), ("kv_D", c_int), ("kv_page_stride", c_ll),
-                ("kv_dtype", c_int), ("kv_k_inv_scale", c_float), ("kv_v_inv_scale", c_float)]
+                ("kv_dtype", c_int), ("kv_k_inv_scale", c_float), ("kv_v_inv_scale", c_float),
+                ("kv_rope", c_void_p), ("kv_rope_len", c_int)]
 
 
 class PaDecodeOptions(ctypes.Structure):
@@ -96,6 +97,11 @@ _SIGS = {
     "llm_decoder_create_kv": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
     "llm_decoder_set_kv_scales": (c_int, [c_void_p, c_void_p, c_void_p]),
     "llm_decoder_kv_dtype": (c_int, [c_void_p]),
+    "llm_rope_table": (c_int, [ctypes.c_double, c_int, c_int, c_void_p]),
+    "rope_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                          c_void_p]),
+    "llm_decoder_set_rope": (c_int, [c_void_p, c_void_p]),
+    "llm_decoder_rope": (c_int, [c_void_p]),
     "llm_decoder_prefill_kernel": (c_int, [c_void_p]),
     "llm_decoder_destroy": (None, [c_void_p]),
     "llm_decoder_begin_synthetic": (c_int, [c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
@@ -560,3 +566,11 @@ def layernorm_quant(x, gamma, beta, eps=1e-5, quant=True, stream=None):
     check(lib.layernorm_quant(ptr(x), R, C, ptr(gamma), ptr(beta), eps, ptr(out), ptr(q), ptr(s),
                               stream_ptr(stream)))
     return out, q, s
+
+
+def rope_table(theta: float, head_dim: int, num_pos: int):
+    """llm_rope_table: float32 [num_pos][head_dim] of (cos, sin) pairs."""
+    import numpy as np
+    out = np.empty((max(num_pos, 0), max(head_dim, 0)), dtype=np.float32)
+    check(load().llm_rope_table(theta, head_dim, num_pos, out.ctypes.data))
+    return out
