@@ -154,6 +154,26 @@ int pa_decode_grouped(const pa_kv_view* kv, const float* q, float* out, const in
                       int pages_per_split, int row_group, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* pa_decode over a sliding window: row b attends to its last `window` tokens,
+ *   max(0, T_b - window) <= t < T_b
+ * (T_b counts the row's own token), whose page is present; the maths is
+ * pa_decode's over those keys.  window 0 is off and window < 0 is
+ * LLM_ERR_INVALID.  Rows are ungrouped (pa_decode_grouped and pa_decode_ex
+ * take no window).  The tiles below a row's window are never read: their
+ * table entries may be -1 (kv_cache_release_before) and their pages may hold
+ * anything.  The splits are cut over the window, not the context: split s of
+ * a row starts s split lengths after the tile that holds T_b - window, and the
+ * plan sizes the splits for ceil(window / page_size) + 1 tiles, the most a
+ * window touches.  With window >= T the launch, its plan and its output bits
+ * are pa_decode's.  Workspace as pa_decode (pa_decode_workspace_bytes). */
+int pa_decode_window(const pa_kv_view* kv, const float* q, float* out, const int32_t* beam_ids,
+                     const int32_t* context_lens, int B, int H, int D, int T, float sm_scale,
+                     int pages_per_split, int window, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* pa_decode_plan for a pa_decode_window call (row_group 1). */
+int pa_decode_window_plan(const pa_kv_view* kv, int B, int H, int D, int T, int pages_per_split,
+                          int window, int* nsplit, int* form);
+
 /* Causal paged attention of a prompt chunk: the reference's prefill pass
  * (AttentionCUDA's is_prefill flag, attention/attention_cuda.hpp:21; maths of
  * cpu_paged_attention_forward, attention_cpu/cpu_attention_kernel.cpp:37-129,
@@ -175,6 +195,17 @@ size_t pa_prefill_workspace_bytes(const pa_kv_view* kv, int p0, int m);
 int pa_prefill(const pa_kv_view* kv, const float* q, int q_stride, float* out, int out_stride,
                int row, int p0, int m, float sm_scale, void* workspace, size_t workspace_bytes,
                void* stream);
+/* pa_prefill over a sliding window: query i attends to positions
+ * max(0, p0 + i - window + 1) .. p0 + i.  Equals pa_decode_window with B = m,
+ * beam_ids[i] = row, context_lens[i] = p0 + i + 1 (within 1e-3 relative).
+ * window 0 is off (pa_prefill itself), window < 0 LLM_ERR_INVALID.  The key
+ * blocks below the chunk's first visible position are not read.  The
+ * workspace size is pa_prefill_workspace_bytes' (an upper bound: the key
+ * split is planned over the whole range, and the splits wholly below the
+ * window cost no reads). */
+int pa_prefill_window(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                      int out_stride, int row, int p0, int m, float sm_scale, int window,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* pa_prefill over prompt chunks of SEVERAL sequences in one launch.  The m =
  * sum(len) query rows are dense in q / out (strides and alignment as
@@ -215,6 +246,13 @@ size_t pa_prefill_packed_workspace_bytes(const pa_kv_view* kv, const pa_prefill_
 int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_stride, float* out,
                       int out_stride, const pa_prefill_seg* segs, int nseg, float sm_scale,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* pa_prefill_packed over a sliding window: row i of segment j equals
+ * pa_prefill_window(row, p0, len) row i, in the one-pass form bit for bit.
+ * Workspace sizes as pa_prefill_packed. */
+int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                             int out_stride, const pa_prefill_seg* segs, int nseg,
+                             float sm_scale, int window, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* The optional stages of the reference attention, CPUAttentionInput /
  * CPUAttentionOutput (attention_cpu/attention_cpu.hpp:8-43) as used by
@@ -429,6 +467,17 @@ int kv_cache_fork(kv_cache* c, int src_beam, int dst_beam);
 int kv_cache_reorder(kv_cache* c, int first_beam, int n, const int32_t* parent, int n_tokens);
 /* Release every page of `beam` (refcount-aware). */
 int kv_cache_release(kv_cache* c, int beam);
+/* Release the pages of `beam` that lie wholly below token n_tokens: tiles
+ * < n_tokens / page_size, all layers and heads (refcount-aware: a page a
+ * forked beam still shares stays allocated until its last owner lets go).
+ * The entries become -1 (dirty: the next kv_cache_sync pushes them; no
+ * longer LRU candidates), which attention reads as missing.  What a
+ * sliding-window decoder calls as its rows advance.  Idempotent, and cheap
+ * when repeated: a per-beam mark of the tiles already released is kept, so a
+ * call walks the newly dead tiles only (any later write of a page below the
+ * mark -- reserve, assign, fork into the beam, a snapshot load -- lowers it
+ * again).  n_tokens <= 0 is a no-op; a beam out of range LLM_ERR_INVALID. */
+int kv_cache_release_before(kv_cache* c, int beam, int n_tokens);
 /* PageTable::clear (page_table.cpp:39-44): all entries -1, all pages free. */
 int kv_cache_clear(kv_cache* c);
 /* PageTable::sync_to_gpu (page_table.cpp:59-62): push dirty host entries.
@@ -528,6 +577,22 @@ int llm_decoder_set_rope(llm_decoder* d, const float* table);
 /* 1: a rotary table is set, 0: none, -1 for NULL
  * (attention/attention_kernel_utils.cuh:20-35). */
 int llm_decoder_rope(const llm_decoder* d);
+/* Sliding-window attention of the decoder: every layer's attention at
+ * position p reads positions max(0, p - window + 1) .. p only -- decode steps
+ * (pa_decode_window), prompt chunks and packed prefill passes
+ * (pa_prefill_window / pa_prefill_packed_window, or the decode kernel where
+ * llm_decoder_prefill_kernel says LLM_PREFILL_DECODE).  window 0 (the default)
+ * is off.  As a row advances, the pages wholly below its window are released
+ * (kv_cache_release_before) before each step and each prefill pass, so a pool
+ * of about ceil((window + 512) / page_size) + 1 tiles per (row, layer, head)
+ * carries a row to max_seq_len, which still bounds positions.  Allowed only
+ * while no rows are active, else LLM_ERR_INVALID; window < 0 LLM_ERR_INVALID.
+ * With a window set, llm_decoder_begin_beams and llm_decoder_beam_search
+ * return LLM_ERR_UNSUPPORTED (any beam width).  The window is stored in no
+ * file. */
+int llm_decoder_set_window(llm_decoder* d, int window);
+/* The decoder's window (0: off), -1 for NULL. */
+int llm_decoder_window(const llm_decoder* d);
 /* The attention kernel prompt chunks (llm_decoder_prefill, the prompts of
  * llm_decoder_generate) of this decoder's pools take: LLM_PREFILL_MFMA
  * (pa_prefill: fp16 or LLM_FP8 pools, head_dim 64 or 128, page_size 16 or 32)

@@ -393,6 +393,10 @@ class Decoder {
     check(llm_decoder_set_rope(d_, a.data()));
   }
   bool rope() const { return llm_decoder_rope(d_) == 1; }
+  // llm_decoder_set_window: sliding-window attention over the last `window`
+  // positions (0: off), before any rows are active
+  void set_window(int window) { check(llm_decoder_set_window(d_, window)); }
+  int window() const { return llm_decoder_window(d_); }
   std::string kv_dtype() const {
     return llm_decoder_kv_dtype(d_) == LLM_FP8 ? "float8_e4m3fn" : "float16";
   }
@@ -485,6 +489,11 @@ class KVTileCache {
     check(kv_cache_reorder(c_, first_beam, (int)parent.size(), parent.data(), n_tokens));
   }
   void release(int beam) { need(); check(kv_cache_release(c_, beam)); }
+  // kv_cache_release_before: the pages of the tiles wholly below token n_tokens
+  void release_before(int beam, int n_tokens) {
+    need();
+    check(kv_cache_release_before(c_, beam, n_tokens));
+  }
   void sync_page_table_to_gpu() { need(); check(kv_cache_sync(c_, nullptr)); check(llm_sync()); }
   // KVTileCache::save_to_file / load_from_file (kv_tile_cache.cpp:105-125):
   // format "pools" (default) is the reference's file byte for byte (raw K pool
@@ -577,6 +586,12 @@ class PageTable {
   int lookup(int beam, int head, int tile) const { need(); return kv_cache_lookup(c_, 0, beam, head, tile); }
   void remove(int beam, int head, int tile) { need(); check(kv_cache_remove(c_, 0, beam, head, tile)); }
   void sync_to_gpu() { need(); check(kv_cache_sync(c_, nullptr)); }
+  // kv_cache_release_before (a PageTable's tiles are one token each): entries
+  // of tiles < n_tiles become -1 on the host; sync_to_gpu pushes them
+  void release_before(int beam, int n_tiles) {
+    need();
+    check(kv_cache_release_before(c_, beam, n_tiles));
+  }
   uintptr_t device_data() const { need(); return reinterpret_cast<uintptr_t>(kv_cache_page_table(c_, 0)); }
 
  private:
@@ -638,6 +653,8 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("set_rope", &Decoder::set_rope, py::arg("table") = py::ellipsis(),
              py::arg("theta") = 10000.0)
         .def_property_readonly("rope", &Decoder::rope)
+        .def("set_window", &Decoder::set_window, py::arg("window"))
+        .def_property_readonly("window", &Decoder::window)
         .def_property_readonly("kv_dtype", &Decoder::kv_dtype)
         .def_property_readonly("prefill_kernel", &Decoder::prefill_kernel)
         .def_property_readonly("kv_handle", &Decoder::kv_handle);
@@ -677,6 +694,7 @@ PYBIND11_MODULE(llm_decoder, m) {
       .def("reorder", &KVTileCache::reorder, py::arg("first_beam"), py::arg("parent"),
            py::arg("n_tokens"))
       .def("release", &KVTileCache::release)
+      .def("release_before", &KVTileCache::release_before, py::arg("beam"), py::arg("n_tokens"))
       .def("sync_page_table_to_gpu", &KVTileCache::sync_page_table_to_gpu)
       .def("save_to_file", &KVTileCache::save_to_file, py::arg("path"),
            py::arg("format") = "pools")
@@ -700,6 +718,7 @@ PYBIND11_MODULE(llm_decoder, m) {
       .def("lookup", &PageTable::lookup)
       .def("remove", &PageTable::remove)
       .def("sync_to_gpu", &PageTable::sync_to_gpu)
+      .def("release_before", &PageTable::release_before, py::arg("beam"), py::arg("n_tiles"))
       .def("device_data", &PageTable::device_data);
 
   m.def("paged_attention",

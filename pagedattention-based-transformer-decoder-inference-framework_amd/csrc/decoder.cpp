@@ -101,6 +101,10 @@ struct llm_decoder {
   // and is stored in no file.
   DevBuf<float> rope;
   bool rope_on = false;
+  // sliding-window attention (llm_decoder_set_window; 0: off): every attention
+  // launch takes it, and the pages wholly below a row's window are released
+  // before each step / prefill pass
+  int window = 0;
 
   // activations / state
   DevBuf<float> x, qkv, o, h1, logits, sa;
@@ -357,6 +361,19 @@ extern "C" int llm_decoder_set_rope(llm_decoder* d, const float* table) {
 }
 
 extern "C" int llm_decoder_rope(const llm_decoder* d) { return d ? (d->rope_on ? 1 : 0) : -1; }
+
+extern "C" int llm_decoder_set_window(llm_decoder* d, int window) {
+  LLM_REQUIRE(d, "llm_decoder_set_window: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_window: rows are active (set the window before "
+                             "begin_* / generate / prefill)");
+  LLM_REQUIRE(window >= 0, "llm_decoder_set_window: window must be >= 0 (0: off)");
+  d->window = window;
+  d->graph_batch = -1;  // the step graph carries the window as a kernel argument
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_window(const llm_decoder* d) { return d ? d->window : -1; }
 
 extern "C" void llm_decoder_destroy(llm_decoder* d) {
   if (!d) return;
@@ -684,6 +701,7 @@ int llm_decoder::attn_request(const Rows& R, pa_kv_view* view, PaRequest* rq, in
   *rq = pa_request(view, R.n, H, D, cfg.max_seq_len, pps, R.row_group, out);
   rq->rows16 = out == PaOut::OPROJ && tap_q;  // the taps read the packed o_proj input
   rq->steal_ctr = R.row_group >= 4 && beam_steal_on();
+  rq->window = window;
   return LLM_OK;
 }
 
@@ -722,9 +740,9 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
     if (R.prefill_ntile > 0)
       return pa_prefill_packed_internal(&view, R.q, hid, R.o, hid, R.prefill_tiles,
                                         R.prefill_ntile, R.ctx, R.n, R.prefill_maxend, sm,
-                                        R.attn_ws, R.attn_ws_bytes, st, &ro);
+                                        R.attn_ws, R.attn_ws_bytes, st, &ro, window);
     return pa_prefill_internal(&view, R.q, hid, R.o, hid, R.prefill_row, R.prefill_p0, R.n, sm,
-                               R.attn_ws, R.attn_ws_bytes, st, &ro);
+                               R.attn_ws, R.attn_ws_bytes, st, &ro, window);
   }
   RET_IF(pa_decode_internal(&view, rq, R.q, hid, R.o, R.beam_rows, R.ctx, sm, R.attn_ws,
                             R.attn_ws_bytes, st, &ro));
@@ -900,6 +918,8 @@ int llm_decoder::run_step(const int32_t* tokens_host, float* logits_dev, int32_t
     for (int b = 0; b < batch; ++b) {
       LLM_REQUIRE(h_pos[b] < cfg.max_seq_len, "decoder: row reached max_seq_len");
       RET_IF(k->prepare_append(b, h_pos[b]));
+      // windowed: the step attends to tokens >= h_pos[b] + 1 - window only
+      if (window > 0) RET_IF(k->release_before(b, h_pos[b] + 1 - window));
     }
     RET_IF(k->sync(st));
   }
@@ -1058,8 +1078,12 @@ int llm_decoder::prefill_pass(const std::vector<PassSeg>& segs, bool packed, hip
   {
     KvCache* k = kv_impl(kv);
     std::lock_guard<std::mutex> gk(k->mu);
-    for (const PassSeg& s : segs)
+    for (const PassSeg& s : segs) {
+      // windowed: the segment's first query sees tokens >= p0 - window + 1, the
+      // later ones no earlier (released first: the pass may need those pages)
+      if (window > 0) RET_IF(k->release_before(s.row, s.p0 - window + 1));
       for (int t = s.p0; t < s.p0 + s.len; t = (t / TS + 1) * TS) RET_IF(k->prepare_append(s.row, t));
+    }
     RET_IF(k->sync(st));
   }
   LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), ((size_t)4 * CAP + 4 * ntile) * sizeof(int32_t),
@@ -1247,6 +1271,9 @@ extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_wi
                   beam_len >= 0,
               "llm_decoder_begin_beams: bad arguments (beam_width in [1, 4])");
   std::lock_guard<std::mutex> g(d->mu);
+  if (d->window > 0)
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_begin_beams: the decoder has a sliding window "
+                                     "(llm_decoder_set_window): beam groups take none");
   const int ctx_len = shared_len + beam_len;
   LLM_REQUIRE(ctx_len < d->cfg.max_seq_len,
               "llm_decoder_begin_beams: shared_len + beam_len must be < max_seq_len");
@@ -1509,6 +1536,9 @@ extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
   LLM_REQUIRE(max_len + max_new - 1 <= d->cfg.max_seq_len,
               "llm_decoder_beam_search: prompt + max_new_tokens exceeds max_seq_len");
   std::lock_guard<std::mutex> g(d->mu);
+  if (d->window > 0)
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_beam_search: the decoder has a sliding window "
+                                     "(llm_decoder_set_window): beam groups take none");
   LLM_REQUIRE(d->weights_ready, "llm_decoder_beam_search: weights not loaded");
   // the step graph's token choice becomes the beam selection for the length
   // of the search (a sampling mode is untouched: beam mode takes precedence)

@@ -81,6 +81,7 @@ int KvCache::init(int L_, int beams_, int H_, int D_, int TS_, int max_tiles_, l
   h_table.assign(entries, -1);
   dirty_flag.assign(entries, 0);
   refcount.assign((size_t)num_pages, 0);
+  low_tile.assign((size_t)beams, 0);
   reset_free_lists();
   LLM_HIP_RET(hipEventCreateWithFlags(&staging_done, hipEventDisableTiming));
   return LLM_OK;
@@ -111,6 +112,35 @@ void KvCache::set_entry(size_t idx, int32_t page) {
     dirty_flag[idx] = 1;
     dirty.push_back((int64_t)idx);
   }
+  if (page >= 0 && low_marks > 0) {  // a page below the beam's release mark: the mark falls to it
+    const int tile = (int)(idx % max_tiles);
+    int& low = low_tile[(idx / max_tiles / H) % beams];
+    if (tile < low) {
+      low = tile;
+      if (low == 0) --low_marks;
+    }
+  }
+}
+
+// kv_cache_release_before: tiles [low_tile[beam], n_tokens / TS) of every
+// layer and head.  Caller holds mu.
+int KvCache::release_before(int beam, int n_tokens) {
+  if (n_tokens <= 0) return LLM_OK;
+  const int end = std::min(n_tokens / TS, max_tiles);
+  int& low = low_tile[beam];
+  if (end <= low) return LLM_OK;
+  for (int l = 0; l < L; ++l)
+    for (int h = 0; h < H; ++h)
+      for (int t = low; t < end; ++t) {
+        const size_t i = index(l, beam, h, t);
+        if (h_table[i] >= 0) {
+          drop_page(h_table[i]);
+          set_entry(i, -1);
+        }
+      }
+  if (low == 0) ++low_marks;
+  low = end;
+  return LLM_OK;
 }
 
 void KvCache::reset_free_lists() {
@@ -531,7 +561,17 @@ extern "C" int kv_cache_release(kv_cache* c, int beam) {
           k.set_entry(i, -1);
         }
       }
+  if (k.low_tile[beam] > 0) --k.low_marks;
+  k.low_tile[beam] = 0;
   return LLM_OK;
+}
+
+extern "C" int kv_cache_release_before(kv_cache* c, int beam, int n_tokens) {
+  LLM_REQUIRE(c, "kv_cache_release_before: NULL");
+  KvCache& k = c->impl;
+  std::lock_guard<std::mutex> g(k.mu);
+  LLM_REQUIRE(beam >= 0 && beam < k.beams, "kv_cache_release_before: bad beam");
+  return k.release_before(beam, n_tokens);
 }
 
 extern "C" int kv_cache_clear(kv_cache* c) {
@@ -547,6 +587,8 @@ extern "C" int kv_cache_clear(kv_cache* c) {
   k.reset_free_lists();
   k.lru.clear();
   k.lru_pos.clear();
+  std::fill(k.low_tile.begin(), k.low_tile.end(), 0);
+  k.low_marks = 0;
   LLM_HIP_RET(hipMemset(k.d_table, 0xFF, k.entries * sizeof(int32_t)));
   LLM_HIP_RET(hipDeviceSynchronize());  // null-stream memset vs. non-blocking user streams
   return LLM_OK;

@@ -63,6 +63,14 @@ struct KvCache {
   void lru_touch(size_t idx);
   void lru_forget(size_t idx);
   bool lru_evict_one();  // false: nothing left to evict
+  // kv_cache_release_before's low-water mark: every tile < low_tile[beam] of
+  // `beam` is -1 in every layer and head, so a call walks tiles from there.
+  // set_entry lowers it when it puts a page on a tile below it (reserve,
+  // assign, fork into the beam, reorder); kv_cache_release / kv_cache_clear
+  // (and with it a snapshot load) reset it to 0.
+  std::vector<int> low_tile;
+  int low_marks = 0;  // beams whose mark is above 0 (none: set_entry has nothing to lower)
+  int release_before(int beam, int n_tokens);
 
   ~KvCache();
   int init(int L, int beams, int H, int D, int TS, int max_tiles, long long pages,

@@ -27,6 +27,7 @@ struct PaMergeRowArgs {
   int pack;  // q / out16 in packed-A order (common.hpp a_frag_off_*)
   int ctx_p0;  // >= 0 and context_lens NULL: row b's context is ctx_p0 + b + 1 (prefill)
   float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
+  int window;  // the split launch's (PaSplitArgs::window): splits relative to the row's window
 };
 
 // One head's split merge (flash-decoding LSE combine) by one wave, DPL =
@@ -117,6 +118,7 @@ struct PaMergeArgs {
   const int32_t* context_lens;
   int B, H, D, T, TS, pps, nsplit, max_tiles;
   float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
+  int window;  // the split launch's (PaSplitArgs::window): splits relative to the row's window
 };
 
 template <int DPL>
@@ -128,9 +130,9 @@ __global__ __launch_bounds__(256) void pa_merge_kernel(PaMergeArgs a) {
   int Tb = a.context_lens ? a.context_lens[b] : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + a.TS - 1) / a.TS, a.max_tiles);
-  const int pps = row_pps(a.pps, a.nsplit, ntiles);
   // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
-  const int ns = a.pps < 0 ? a.nsplit : min(a.nsplit, (ntiles + pps - 1) / pps);
+  const int ns = a.pps < 0 ? a.nsplit
+                           : row_nsplits(a.pps, a.nsplit, row_span(Tb, ntiles, a.window, a.TS).n_live);
   float acc[DPL];
   const float inv = a.out_scale * merge_head<DPL, 16>(a.part_ml + (size_t)bh * a.nsplit * 2,
                                                       a.part_acc + (size_t)bh * a.nsplit * a.D,
@@ -158,9 +160,9 @@ __global__ __launch_bounds__(1024) void pa_merge_row_kernel(PaMergeRowArgs a) {
   int Tb = a.context_lens ? a.context_lens[b] : a.ctx_p0 >= 0 ? a.ctx_p0 + b + 1 : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + a.TS - 1) / a.TS, a.max_tiles);
-  const int pps = row_pps(a.pps, a.nsplit, ntiles);
   // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
-  const int ns = a.pps < 0 ? a.nsplit : min(a.nsplit, (ntiles + pps - 1) / pps);
+  const int ns = a.pps < 0 ? a.nsplit
+                           : row_nsplits(a.pps, a.nsplit, row_span(Tb, ntiles, a.window, a.TS).n_live);
   for (int h = w; h < a.H; h += nw) {
     const size_t bh = (size_t)b * a.H + h;
     float acc[DPL];
@@ -375,9 +377,9 @@ extern "C" size_t pa_decode_workspace_bytes(int B, int H, int D, int max_tiles,
 int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                                   const int32_t* context_lens, int B, int H, int D, int T, int TS,
                                   int pps, int nsplit, int max_tiles, hipStream_t st,
-                                  float out_scale) {
+                                  float out_scale, int window) {
   PaMergeArgs mg{part_acc, part_ml, out, context_lens, B, H, D, T, TS, pps, nsplit, max_tiles,
-                 out_scale};
+                 out_scale, window};
   const dim3 grid((B * H + 3) / 4);
   if (D <= 64)
     hipLaunchKernelGGL(pa_merge_kernel<1>, grid, dim3(256), 0, st, mg);
@@ -392,11 +394,11 @@ int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, f
 int llm::pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                                 const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                                 int B, int H, int D, int T, int TS, int pps, int nsplit,
-                                int max_tiles, hipStream_t st, float out_scale) {
+                                int max_tiles, hipStream_t st, float out_scale, int window) {
   PaMergeRowArgs mg{part_acc, part_ml, out, rows ? rows->q : nullptr,
                     rows ? rows->inv_scale : nullptr,
                     rows ? static_cast<_Float16*>(rows->out16) : nullptr, context_lens, B, H, D, T,
-                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0, out_scale};
+                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0, out_scale, window};
   const int threads = 64 * std::min(16, H);  // one wave per head (heads > 16 loop)
   const size_t lds = (size_t)H * D * sizeof(float);
   if (D <= 64)
@@ -416,6 +418,10 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
   const int B = rq.B, H = rq.H, D = rq.D, T = rq.T;
   LLM_REQUIRE(kv != nullptr, "pa_decode: kv view is NULL");
   LLM_REQUIRE(B >= 0 && H > 0 && D > 0 && T >= 0, "pa_decode: bad B/H/D/T");
+  LLM_REQUIRE(rq.window >= 0, "pa_decode: window must be >= 0 (0: off)");
+  if (rq.window > 0 && rq.row_group > 1)
+    return fail(LLM_ERR_UNSUPPORTED, "pa_decode: a sliding window needs ungrouped rows "
+                                     "(row_group 1)");
   if (plan) *plan = PaLaunch{};
   if (B == 0) return LLM_OK;
   // the FP16 decoder's fused o_proj (PaRowOutputs::o_acc): workgroup-merge launches only
@@ -478,6 +484,7 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
   a.qscale = sm_scale * kLog2e;
   const float out_scale = rows && kv->kv_dtype == LLM_FP8 ? rows->out_scale : 1.f;
   a.out_scale = out_scale;
+  a.window = rq.window;
   if (!p.direct && !p.wgm) {  // (the workgroup merge keeps its splits' states in LDS)
     LLM_REQUIRE(workspace != nullptr && workspace_bytes >= p.workspace_bytes,
                 "pa_decode: workspace too small (see pa_decode_workspace_bytes)");
@@ -515,11 +522,11 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
   if (row_out && !p.direct)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, rows->keep_out ? out : nullptr, rows,
                                   context_lens, -1, B, H, D, T, TS, p.beam ? -1 : p.pps, p.nsplit,
-                                  kv->max_tiles, st, out_scale);
+                                  kv->max_tiles, st, out_scale, rq.window);
   if (!p.direct) {
     const int r = pa_merge_splits_internal(a.part_acc, a.part_ml, out, context_lens, B, H, D, T,
                                            TS, p.beam ? -1 : p.pps, p.nsplit, kv->max_tiles, st,
-                                           out_scale);
+                                           out_scale, rq.window);
     if (r != LLM_OK) return r;
   }
   if (row_out) {  // single split: out is final; convert it in a row pass
@@ -562,4 +569,27 @@ extern "C" int pa_decode(const pa_kv_view* kv, const float* q, float* out,
   return pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split), q, H * D, out,
                             beam_ids, context_lens, sm_scale, workspace, workspace_bytes,
                             as_stream(stream));
+}
+
+extern "C" int pa_decode_window_plan(const pa_kv_view* kv, int B, int H, int D, int T,
+                                     int pages_per_split, int window, int* nsplit, int* form) {
+  LLM_REQUIRE(nsplit && form, "pa_decode_window_plan: NULL output");
+  PaLaunch p;
+  const int rc = pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split, 1, PaOut::F32,
+                                                   window),
+                                    nullptr, H * D, nullptr, nullptr, nullptr, 1.f, nullptr, 0,
+                                    nullptr, nullptr, &p);
+  *nsplit = p.nsplit;
+  *form = p.form();
+  return rc;
+}
+
+extern "C" int pa_decode_window(const pa_kv_view* kv, const float* q, float* out,
+                                const int32_t* beam_ids, const int32_t* context_lens, int B,
+                                int H, int D, int T, float sm_scale, int pages_per_split,
+                                int window, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return pa_decode_internal(kv, pa_request(kv, B, H, D, T, pages_per_split, 1, PaOut::F32, window),
+                            q, H * D, out, beam_ids, context_lens, sm_scale, workspace,
+                            workspace_bytes, as_stream(stream));
 }

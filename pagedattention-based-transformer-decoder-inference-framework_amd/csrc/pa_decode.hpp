@@ -52,13 +52,14 @@ constexpr int kv_elem_size(int kvt) {
 
 // The request (pa_plan.hpp) of a launch over a view's pages.
 inline PaRequest pa_request(const pa_kv_view* kv, int B, int H, int D, int T, int pages_per_split,
-                            int row_group = 1, PaOut out = PaOut::F32) {
+                            int row_group = 1, PaOut out = PaOut::F32, int window = 0) {
   PaRequest rq;
   rq.B = B, rq.H = H, rq.D = D, rq.T = T;
   if (kv) rq.TS = kv->page_size, rq.max_tiles = kv->max_tiles, rq.kv_dtype = kv->kv_dtype;
   rq.pps_fixed = pages_per_split > 0 ? std::min(pages_per_split, kMaxPps) : 0;
   rq.row_group = row_group;
   rq.out = out;
+  rq.window = window;
   return rq;
 }
 
@@ -92,17 +93,18 @@ bool beam_steal_on();
 // Split merge of per-(row, head, split) partial softmax states into rows
 // (out fp32 [B][H*D] and/or the rows->q / out16 o_proj inputs); row b's
 // context is context_lens[b], or ctx_p0 + b + 1 when context_lens is NULL and
-// ctx_p0 >= 0, or T.  Split s of a row covers tiles [s*pps, (s+1)*pps).
+// ctx_p0 >= 0, or T.  Split s of a row covers tiles [s*pps, (s+1)*pps), counted
+// from the row's first live tile under `window` (pa_split.hpp row_span; 0: none).
 // out_scale multiplies every merged head (LLM_FP8 pools: the V scale).
 int pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                            const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                            int B, int H, int D, int T, int TS, int pps, int nsplit, int max_tiles,
-                           hipStream_t st, float out_scale = 1.f);
+                           hipStream_t st, float out_scale = 1.f, int window = 0);
 
 int pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                              const int32_t* context_lens, int B, int H, int D, int T, int TS,
                              int pps, int nsplit, int max_tiles, hipStream_t st,
-                             float out_scale = 1.f);
+                             float out_scale = 1.f, int window = 0);
 
 // Causal MFMA attention of a prompt chunk (csrc/pa_prefill.hip, C entry
 // pa_prefill): out rows i < m = attention of query i (position p0 + i) over
@@ -111,11 +113,13 @@ int pa_merge_splits_internal(const float* part_acc, const float* part_ml, float*
 // workgroups and merged by pa_merge_rows_internal, which also writes `rows`
 // (the o_proj input); without, one pass writes out and `rows` is converted by
 // the row quantiser.  `out` may be NULL only when it splits and rows is set.
+// window > 0: query i attends to positions max(0, p0 + i - window + 1) .. p0 + i.
 bool pa_prefill_supported(const pa_kv_view* kv);
 size_t pa_prefill_ws_bytes(const pa_kv_view* kv, int p0, int m);
 int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
                         int out_stride, int row, int p0, int m, float sm_scale, void* workspace,
-                        size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows = nullptr);
+                        size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows = nullptr,
+                        int window = 0);
 
 // The packed form (C entry pa_prefill_packed): m dense rows of q / out made of
 // segments of several sequences, driven by a device tile table
@@ -130,7 +134,7 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
                                int out_stride, const int32_t* tiles_dev, int ntile,
                                const int32_t* ctx_dev, int m, int maxend, float sm_scale,
                                void* part_ws, size_t part_bytes, hipStream_t st,
-                               const PaRowOutputs* rows = nullptr);
+                               const PaRowOutputs* rows = nullptr, int window = 0);
 
 // Bytes from page p to page p + 1 of a view's pools (page_stride 0 = dense).
 inline size_t kv_view_page_stride(const pa_kv_view& v) {

@@ -52,6 +52,9 @@ struct PaRequest {
   bool rows16 = false;    // OPROJ: the fp16 rows as well (the decoder's taps)
   bool steal_ctr = false;  // beam groups: the caller owns steal counters (PaRowOutputs::beam_ctr)
   bool keep_out = true;   // row outputs: a split launch writes the fp32 rows as well
+  // sliding window: row b attends to its last `window` tokens only (0: off, the
+  // whole context); ungrouped rows only
+  int window = 0;
 };
 
 struct PaLaunch {
@@ -126,14 +129,20 @@ inline int choose_nsplit(int B, int H, int ntiles, int pps_fixed, long long resi
 // chip's resident waves of the plain split kernel, of the beam form (0 where
 // the plain schedule runs instead) and of the tuning build's pa_beam4_kernel;
 // read only for dynamic splits (pps_fixed 0).  LLM_ERR_UNSUPPORTED: the row
-// needs more than kMaxSplits splits of kMaxPps pages.
+// needs more than kMaxSplits splits of kMaxPps pages, or a window is asked
+// for grouped rows.
 inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
                    long long beam_resident, long long beam4_resident, PaLaunch* out) {
   const int B = rq.B, H = rq.H, D = rq.D, TS = rq.TS, row_group = rq.row_group, kvt = rq.kv_dtype;
   const bool oproj = rq.out == PaOut::OPROJ, f32_rows = rq.out == PaOut::F32_ROWS;
   const bool out16 = rq.out == PaOut::ROW_F16 || (oproj && rq.rows16);
   // tiles at or past max_tiles have no page-table entry: they are missing (masked)
-  const int ntiles_max = std::max(1, std::min((rq.T + TS - 1) / TS, rq.max_tiles));
+  int ntiles_max = std::max(1, std::min((rq.T + TS - 1) / TS, rq.max_tiles));
+  // a window of W tokens, wherever it starts in its first page, touches at
+  // most ceil(W / TS) + 1 tiles: the splits are sized for those
+  if (rq.window > 0) ntiles_max = std::min(ntiles_max, (rq.window - 1) / TS + 2);
+  *out = PaLaunch{};
+  if (rq.window > 0 && row_group > 1) return LLM_ERR_UNSUPPORTED;
   const int pps_fixed = rq.pps_fixed > 0 ? std::min(rq.pps_fixed, kMaxPps) : 0;
   // the beam-group form: fp16 pages of two register stages
   const bool beam_shape = kvt == LLM_F16 && split_stages(D, TS, 2) == 2;
@@ -205,7 +214,6 @@ inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
       nsplit = (int)ns;
     }
   }
-  *out = PaLaunch{};
   if (nsplit > kMaxSplits || (long long)nsplit * (pps_fixed > 0 ? pps_fixed : kMaxPps) < ntiles_max)
     return LLM_ERR_UNSUPPORTED;
   const int group = std::max(1, std::min(row_group, 4));  // PaSplitArgs::group

@@ -75,6 +75,9 @@ struct PaPrefillArgs {
   // multiplies the normalised head of the one-pass form (LLM_FP8: the V scale;
   // the split form hands it to the merge)
   float out_scale;
+  // sliding window (0: off): the query at position p attends to positions
+  // max(0, p - window + 1) .. p
+  int window;
 };
 
 constexpr int kKeyBlock = 32;
@@ -149,6 +152,26 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   const int nblk = min((split + 1) * a.pps * TS / KB, lastpos / KB + 1);
   // no query of this workgroup reaches this split: the merge never reads it
   if (kb0 >= nblk) return;
+  // Window: wlo = the first key any query of the tile sees (its first query's
+  // first visible position), qlo = this lane's query's.  The key-block loop
+  // starts at wlo's block.  The splits stay absolute (the merge counts a
+  // row's splits from tile 0), so a split wholly below the tile's window
+  // still owes the merge a partial: an empty one, (m, l, acc) = (sentinel, 0,
+  // 0), written without reading any K/V.
+  const int wlo = a.window > 0 ? max(0, p0 - a.window + 1) : 0;
+  const int qlo = a.window > 0 ? qpos - a.window + 1 : 0;
+  const int kbs = max(kb0, wlo / KB);
+  if (kbs >= nblk) {  // (split form only: one pass ends at lastpos >= wlo)
+    if (qok && a.part_acc) {
+      const size_t pidx = ((size_t)qi * a.H + h) * a.nsplit + split;
+      float* o = a.part_acc + pidx * D + 4 * g;
+#pragma unroll
+      for (int nd = 0; nd < ND; ++nd)
+        *reinterpret_cast<f32x4*>(o + 16 * nd) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (g == 0) *reinterpret_cast<float2*>(a.part_ml + pidx * 2) = float2{kNegSentinel, 0.f};
+    }
+    return;
+  }
   const int32_t* pt = pt_row + (size_t)h * a.max_tiles;
 
   // Q^T B-operand fragments: lane holds q[qi][32kk + 8g .. +7] (pre-scaled by
@@ -195,9 +218,15 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   using Chunk = typename std::conditional<FP8, u32x2, u32x4>::type;  // 8 pool elements
   Chunk kr[CPT], vr[CPT];
   int vok[CPT];
-  auto page_of = [&](int kg) -> int {  // page of key position kg, -1 if none / past lastpos
+  // page of key position kg, -1 if none / past lastpos / below the tile's window.
+  // Keys in [wlo, qlo) of a later query of the tile are staged with their real
+  // V and dropped by p = 0 alone: safe because those pages are still live (the
+  // tile's first query sees them, and pages are released only below the first
+  // query's window), so they hold written, finite values.  A release point
+  // above p0 - window + 1 would break that.
+  auto page_of = [&](int kg) -> int {
     const int tile = kg / TS;
-    int pg = (kg <= lastpos && tile < a.max_tiles) ? pt[tile] : -1;
+    int pg = (kg <= lastpos && kg >= wlo && tile < a.max_tiles) ? pt[tile] : -1;
     return (pg >= 0 && pg < a.num_pages) ? pg : -1;
   };
   auto load = [&](int kb) {
@@ -238,9 +267,9 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
   for (int nd = 0; nd < ND; ++nd) O[nd] = f32x4{0.f, 0.f, 0.f, 0.f};
   float mrun = kNegSentinel, lrun = 0.f;
 
-  load(kb0);
-  for (int kb = kb0; kb < nblk; ++kb) {
-    if (kb > kb0) __syncthreads();  // every wave is done reading block kb-1
+  load(kbs);
+  for (int kb = kbs; kb < nblk; ++kb) {
+    if (kb > kbs) __syncthreads();  // every wave is done reading block kb-1
     stage();
     __syncthreads();
     if (kb + 1 < nblk) load(kb + 1);  // next block's loads fly during this block's math
@@ -258,7 +287,7 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
       }
       s[t] *= qinv;
     }
-    // causal + missing-page mask, online softmax (per query = per lane)
+    // causal + window + missing-page mask, online softmax (per query = per lane)
     bool ok[2][4];
     float mloc = kNegSentinel;
 #pragma unroll
@@ -266,7 +295,7 @@ __global__ __launch_bounds__(64 * NW) void pa_prefill_kernel(PaPrefillArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = 16 * t + 4 * g + r;
-        ok[t][r] = kval[key] != 0 && kb * KB + key <= qpos;
+        ok[t][r] = kval[key] != 0 && kb * KB + key <= qpos && kb * KB + key >= qlo;
         if (ok[t][r]) mloc = fmaxf(mloc, s[t][r]);
       }
     mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
@@ -409,8 +438,10 @@ size_t pa_prefill_ws_bytes(const pa_kv_view* kv, int p0, int m) {
 
 int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
                         int out_stride, int row, int p0, int m, float sm_scale, void* workspace,
-                        size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows) {
+                        size_t workspace_bytes, hipStream_t st, const PaRowOutputs* rows,
+                        int window) {
   LLM_REQUIRE(kv && q, "pa_prefill: NULL argument");
+  LLM_REQUIRE(window >= 0, "pa_prefill: window must be >= 0 (0: off)");
   if (!pa_prefill_supported(kv))
     return fail(LLM_ERR_UNSUPPORTED,
                 "pa_prefill: fp16 or FP8 (e4m3) pools with head_dim 64 or 128 and page_size 16 "
@@ -447,6 +478,7 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
   a.num_pages = kv->num_pages;
   a.p0 = p0;
   a.m = m;
+  a.window = window;
   a.qscale = sm_scale * kLog2e;
   if (split) {
     a.nsplit = pl.nsplit;
@@ -465,10 +497,13 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
                            ? launch_prefill_shape<LLM_FP8>(a, D, TS, pl.nw, 0, st)
                            : launch_prefill_shape<LLM_F16>(a, D, TS, pl.nw, 0, st);
   if (e != hipSuccess) return fail(LLM_ERR_HIP, std::string("pa_prefill launch: ") + hipGetErrorString(e));
+  // The merge gets no window: prefill splits are absolute, [s*pps, (s+1)*pps)
+  // from tile 0, and the splits below a query's window hold empty partials
+  // (the kernel writes them), so the merge's count from tile 0 stays right.
   if (split)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, (rows && !rows->keep_out) ? nullptr : out,
                                   rows, nullptr, p0, m, H, D, p0 + m, TS, pl.pps, pl.nsplit,
-                                  kv->max_tiles, st, out_scale);
+                                  kv->max_tiles, st, out_scale, 0);
   if (row_out) {  // one pass: convert the fp32 rows into the o_proj input
     if (rows->q)
       LLM_HIP_RET(launch_quantize_rows(out, m, hid, rows->q, rows->inv_scale, st, rows->pack));
@@ -569,8 +604,9 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
                                int out_stride, const int32_t* tiles_dev, int ntile,
                                const int32_t* ctx_dev, int m, int maxend, float sm_scale,
                                void* part_ws, size_t part_bytes, hipStream_t st,
-                               const PaRowOutputs* rows) {
+                               const PaRowOutputs* rows, int window) {
   LLM_REQUIRE(kv && q && tiles_dev && ctx_dev, "pa_prefill_packed: NULL argument");
+  LLM_REQUIRE(window >= 0, "pa_prefill_packed: window must be >= 0 (0: off)");
   if (!pa_prefill_supported(kv))
     return fail(LLM_ERR_UNSUPPORTED,
                 "pa_prefill_packed: fp16 or FP8 (e4m3) pools with head_dim 64 or 128 and "
@@ -609,6 +645,7 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
   a.max_tiles = kv->max_tiles;
   a.num_pages = kv->num_pages;
   a.m = m;
+  a.window = window;
   a.qscale = sm_scale * kLog2e;
   if (split) {
     a.nsplit = pl.nsplit;
@@ -626,10 +663,12 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
                            : launch_prefill_shape<LLM_F16>(a, D, TS, 4, ntile, st);
   if (e != hipSuccess)
     return fail(LLM_ERR_HIP, std::string("pa_prefill_packed launch: ") + hipGetErrorString(e));
-  if (split)  // a row's context selects the splits its own tile wrote
+  // a row's context selects the splits its own tile wrote (no window for the
+  // merge: absolute splits, empty partials below the window, as pa_prefill's)
+  if (split)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, (rows && !rows->keep_out) ? nullptr : out,
                                   rows, ctx_dev, -1, m, H, D, maxend, TS, pl.pps, pl.nsplit,
-                                  kv->max_tiles, st, out_scale);
+                                  kv->max_tiles, st, out_scale, 0);
   if (row_out) {  // one pass: convert the fp32 rows into the o_proj input
     if (rows->q)
       LLM_HIP_RET(launch_quantize_rows(out, m, hid, rows->q, rows->inv_scale, st, rows->pack));
@@ -672,8 +711,17 @@ extern "C" int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_str
                                  int out_stride, const pa_prefill_seg* segs, int nseg,
                                  float sm_scale, void* workspace, size_t workspace_bytes,
                                  void* stream) {
+  return pa_prefill_packed_window(kv, q, q_stride, out, out_stride, segs, nseg, sm_scale, 0,
+                                  workspace, workspace_bytes, stream);
+}
+
+extern "C" int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, int q_stride,
+                                        float* out, int out_stride, const pa_prefill_seg* segs,
+                                        int nseg, float sm_scale, int window, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
   using namespace llm;
   LLM_REQUIRE(kv && q && out, "pa_prefill_packed: NULL argument");
+  LLM_REQUIRE(window >= 0, "pa_prefill_packed: window must be >= 0 (0: off)");
   PackedShape ps;
   const int rc = packed_shape(kv, segs, nseg, &ps);
   if (rc) return rc;
@@ -713,7 +761,7 @@ extern "C" int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_str
   }
   return pa_prefill_packed_internal(kv, q, qs, out, os, tiles, ps.ntile, ctx, ps.m, ps.maxend,
                                     sm_scale, static_cast<uint8_t*>(workspace) + meta,
-                                    workspace_bytes - meta, st, nullptr);
+                                    workspace_bytes - meta, st, nullptr, window);
 }
 
 extern "C" size_t pa_prefill_workspace_bytes(const pa_kv_view* kv, int p0, int m) {
@@ -723,7 +771,16 @@ extern "C" size_t pa_prefill_workspace_bytes(const pa_kv_view* kv, int p0, int m
 extern "C" int pa_prefill(const pa_kv_view* kv, const float* q, int q_stride, float* out,
                           int out_stride, int row, int p0, int m, float sm_scale, void* workspace,
                           size_t workspace_bytes, void* stream) {
+  return pa_prefill_window(kv, q, q_stride, out, out_stride, row, p0, m, sm_scale, 0, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int pa_prefill_window(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                                 int out_stride, int row, int p0, int m, float sm_scale,
+                                 int window, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
   LLM_REQUIRE(out, "pa_prefill: out is NULL");
   return llm::pa_prefill_internal(kv, q, q_stride, out, out_stride, row, p0, m, sm_scale,
-                                  workspace, workspace_bytes, llm::as_stream(stream));
+                                  workspace, workspace_bytes, llm::as_stream(stream), nullptr,
+                                  window);
 }

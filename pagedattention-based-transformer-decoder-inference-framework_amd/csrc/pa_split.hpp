@@ -109,12 +109,37 @@ struct PaSplitArgs {
   // form and the workgroup merge here, the merge kernels otherwise); K's scale
   // arrives folded into qscale.  Other element types never read it.
   float out_scale;
+  // Sliding window (ungrouped rows; 0: off): row b attends to tokens
+  // [max(0, T_b - window), T_b) only.  Wave-uniform; row_span below turns it
+  // into the row's live tiles.
+  int window;
 };
 
 // Split length of a row with `ntiles` live tiles.
 __device__ __forceinline__ int row_pps(int pps_fixed, int nsplit, int ntiles) {
   if (pps_fixed > 0) return pps_fixed;
   return min(max((ntiles + nsplit - 1) / nsplit, 1), kMaxPps);
+}
+
+// The live tiles of a row of context Tb (ntiles tiles) under a window: tokens
+// t_lo .. Tb - 1, tiles lo_tile .. ntiles - 1.  The splits of a windowed row
+// are relative to lo_tile (split s starts at tile lo_tile + s * pps, pps =
+// row_pps(.., n_live)), so a window deep in a long context is cut like a short
+// context of its own length.  The split kernel and every merge derive a row's
+// split count from THIS function: a merge that counted differently would read
+// partials no split wrote.  window 0: t_lo = lo_tile = 0, n_live = ntiles.
+struct PaSpan {
+  int t_lo, lo_tile, n_live;
+};
+__device__ __forceinline__ PaSpan row_span(int Tb, int ntiles, int window, int TS) {
+  const int t_lo = window > 0 ? max(0, Tb - window) : 0;
+  const int lo_tile = t_lo / TS;
+  return {t_lo, lo_tile, max(ntiles - lo_tile, 0)};
+}
+// Splits of the row that hold a partial: min(nsplit, ceil(n_live / pps)).
+__device__ __forceinline__ int row_nsplits(int pps_fixed, int nsplit, int n_live) {
+  const int pps = row_pps(pps_fixed, nsplit, n_live);
+  return min(nsplit, (n_live + pps - 1) / pps);
 }
 
 // Pages per register stage: CHUNK_BYTES of K+V in flight per wave per stage.
@@ -306,6 +331,12 @@ void pa_split_kernel(PaSplitArgs a) {
   int Tb = a.context_lens ? a.context_lens[b] : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + TS - 1) / TS, a.max_tiles);
+  // (beam-group launches carry no window: the host refuses it)
+  const PaSpan span = row_span(Tb, ntiles, a.window, TS);
+  const int t_lo = span.t_lo;
+  // tiles whose every token is live start at a token in [t_lo, Tb - TS]: one
+  // unsigned compare of (tile * TS - t_lo) against this per page
+  const unsigned full_span = (unsigned)max(Tb - TS - t_lo + 1, 0);
   int tile0, count;
   // tiles of the split: tile0 + j * tstride, j < count
   int tstride = 1;
@@ -314,8 +345,8 @@ void pa_split_kernel(PaSplitArgs a) {
     tstride = a.nsplit;
     count = ntiles > s ? (ntiles - s + a.nsplit - 1) / a.nsplit : 0;
   } else {
-    const int pps = row_pps(a.pps, a.nsplit, ntiles);
-    tile0 = s * pps;
+    const int pps = row_pps(a.pps, a.nsplit, span.n_live);
+    tile0 = span.lo_tile + s * pps;
     count = min(pps, ntiles - tile0);
   }
   // BEAM: the page ids of the group's 4 rows, tiles [0, pfx_lim), read once
@@ -490,7 +521,8 @@ void pa_split_kernel(PaSplitArgs a) {
     }
     // One page u of the chunk.  FULL (wave-uniform): the page is present and
     // every one of its tokens is inside the context, so no token needs the
-    // validity selects (the common case: all but a row's last page).
+    // validity selects (the common case: all but a row's last page and, under
+    // a window, its first live page, whose head lies below t_lo).
     auto page_math = [&](auto full_tag, int u, bool ok, int tok_base) {
       constexpr bool FULL = decltype(full_tag)::value;
       float sc[NI];
@@ -502,7 +534,8 @@ void pa_split_kernel(PaSplitArgs a) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) d = fmaf(qv[e], kv_at<C.kvt>(kk[u * NI + i], e), d);
         d = group_sum<LPT>(d);
-        valid[i] = FULL || (ok && (tok_base + i * TPI) < Tb);
+        // t_lo <= token < Tb in one unsigned compare (t_lo <= Tb, token >= 0)
+        valid[i] = FULL || (ok && (unsigned)(tok_base + i * TPI - t_lo) < (unsigned)(Tb - t_lo));
         sc[i] = valid[i] ? d : kNegSentinel;
         mloc = fmaxf(mloc, sc[i]);
       }
@@ -530,7 +563,7 @@ void pa_split_kernel(PaSplitArgs a) {
       const bool ok = (j < count) && (pg >= 0);
       const int tile = tile0 + j * (IL ? tstride : 1);
       const int tok_base = tile * TS + g;
-      if (C.fullpath && ok && (tile + 1) * TS <= Tb)
+      if (C.fullpath && ok && (unsigned)(tile * TS - t_lo) < full_span)
         page_math(std::true_type{}, u, ok, tok_base);
       else
         page_math(std::false_type{}, u, ok, tok_base);
@@ -762,8 +795,7 @@ void pa_split_kernel(PaSplitArgs a) {
     if (!C.oproj && s != 0) return;
     __shared__ __attribute__((aligned(16))) _Float16 wg_o[C.oproj ? D : 8];
     if (s == 0) {
-      const int pps = row_pps(a.pps, a.nsplit, ntiles);
-      const int ns = min(a.nsplit, (ntiles + pps - 1) / pps);
+      const int ns = row_nsplits(a.pps, a.nsplit, span.n_live);
       const float m0 = lane < ns ? wg_ml[lane][0] : kNegSentinel;
       const float l0 = lane < ns ? wg_ml[lane][1] : 0.f;
       const float M = ln_wave_max(fmaxf(m0, kNegSentinel));

@@ -999,12 +999,14 @@ extern "C" long long pa_tune_stamps(unsigned long long* host, long long max_wave
 // device, any other is taken as given.  The request passes pa_decode_internal's
 // own checks first (over a view of these fields with placeholder pointers,
 // which a plan-only call never reads).
-extern "C" int pa_plan_tune(int B, int H, int D, int T, int page_size, int max_tiles, int kv_dtype,
-                            int pages_per_split, int row_group, int out_kind, int rows16,
-                            long long resident, long long beam_resident, long long beam4_resident,
-                            int* nsplit, int* form) {
-  LLM_REQUIRE(nsplit && form, "pa_plan_tune: NULL output");
-  LLM_REQUIRE(out_kind >= 0 && out_kind <= (int)PaOut::OPROJ, "pa_plan_tune: out_kind");
+// (pa_plan_window_tune: the same with the request's sliding window, PaRequest::window; 0: none.)
+extern "C" int pa_plan_window_tune(int B, int H, int D, int T, int page_size, int max_tiles,
+                                   int kv_dtype, int pages_per_split, int row_group, int window,
+                                   int out_kind, int rows16, long long resident,
+                                   long long beam_resident, long long beam4_resident, int* nsplit,
+                                   int* form) {
+  LLM_REQUIRE(nsplit && form, "pa_plan_window_tune: NULL output");
+  LLM_REQUIRE(out_kind >= 0 && out_kind <= (int)PaOut::OPROJ, "pa_plan_window_tune: out_kind");
   *nsplit = *form = 0;
   static const int32_t placeholder = 0;
   pa_kv_view kv{};
@@ -1016,15 +1018,26 @@ extern "C" int pa_plan_tune(int B, int H, int D, int T, int page_size, int max_t
   kv.kv_dtype = kv_dtype;
   PaRequest rq = pa_request(&kv, B, H, D, T, pages_per_split, row_group, (PaOut)out_kind);
   rq.rows16 = rows16 != 0;
+  rq.window = window;
   PaLaunch p;
   const int rc = pa_decode_internal(&kv, rq, nullptr, H * D, nullptr, nullptr, nullptr, 1.f,
                                     nullptr, 0, nullptr, nullptr, &p);
   if (rc != LLM_OK) return rc;
   if (pa_plan_device(rq, &p, resident, beam_resident, beam4_resident) != LLM_OK)
-    return fail(LLM_ERR_UNSUPPORTED, "pa_plan_tune: more splits than a row may have");
+    return fail(LLM_ERR_UNSUPPORTED, "pa_plan_window_tune: more splits than a row may have");
   *nsplit = p.nsplit;
   *form = p.form();
   return LLM_OK;
+}
+
+// pa_plan_window_tune without a window.
+extern "C" int pa_plan_tune(int B, int H, int D, int T, int page_size, int max_tiles, int kv_dtype,
+                            int pages_per_split, int row_group, int out_kind, int rows16,
+                            long long resident, long long beam_resident, long long beam4_resident,
+                            int* nsplit, int* form) {
+  return pa_plan_window_tune(B, H, D, T, page_size, max_tiles, kv_dtype, pages_per_split, row_group,
+                             0, out_kind, rows16, resident, beam_resident, beam4_resident, nsplit,
+                             form);
 }
 
 // Tuning hook: the prefill pass packer (prefill_pack.hpp) on explicit rows

@@ -109,13 +109,20 @@ _SIGS = {
     "pa_decode_pages_per_split": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pa_decode_plan": (c_int, [ctypes.POINTER(PaKvView), c_int, c_int, c_int, c_int, c_int, c_int,
                                c_i32p, c_i32p]),
+    "pa_decode_window_plan": (c_int, [ctypes.POINTER(PaKvView), c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_i32p, c_i32p]),
     # tuning library only: the launch planner on explicit request fields
     "pa_plan_tune": (c_int, [c_int] * 11 + [c_ll] * 3 + [c_i32p, c_i32p]),
+    # ... and with a sliding window (after row_group)
+    "pa_plan_window_tune": (c_int, [c_int] * 12 + [c_ll] * 3 + [c_i32p, c_i32p]),
     # tuning library only: the prefill pass packer (csrc/prefill_pack.hpp)
     "prefill_passes_tune": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_int]),
     "pa_decode": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_void_p,
                           c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
                           c_void_p]),
+    "pa_decode_window": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
+                                 c_size_t, c_void_p]),
     "pa_decode_grouped": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
                                   c_void_p, c_size_t, c_void_p]),
@@ -126,6 +133,11 @@ _SIGS = {
     "pa_decode_ex_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pa_prefill": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p, c_int, c_int,
                            c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "pa_prefill_window": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p, c_int, c_int,
+                                  c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "pa_prefill_packed_window": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p,
+                                         c_int, ctypes.POINTER(PaPrefillSeg), c_int, c_float,
+                                         c_int, c_void_p, c_size_t, c_void_p]),
     "pa_prefill_packed_tiles": (c_int, [ctypes.POINTER(PaKvView), ctypes.POINTER(PaPrefillSeg),
                                         c_int, c_i32p, c_int]),
     "pa_prefill_packed_workspace_bytes": (c_size_t, [ctypes.POINTER(PaKvView),
@@ -192,6 +204,9 @@ _SIGS = {
     "kv_cache_reserve": (c_int, [c_void_p, c_int, c_int]),
     "kv_cache_fork": (c_int, [c_void_p, c_int, c_int]),
     "kv_cache_release": (c_int, [c_void_p, c_int]),
+    "kv_cache_release_before": (c_int, [c_void_p, c_int, c_int]),
+    "llm_decoder_set_window": (c_int, [c_void_p, c_int]),
+    "llm_decoder_window": (c_int, [c_void_p]),
     "kv_cache_clear": (c_int, [c_void_p]),
     "kv_cache_sync": (c_int, [c_void_p, c_void_p]),
     "kv_cache_write_tokens": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -336,10 +351,12 @@ def kv_view(k_pool, v_pool, page_table, *, num_beams=None) -> PaKvView:
 
 
 def pa_decode(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_lens=None,
-              sm_scale=1.0, pages_per_split=0, out=None, stream=None, row_group=1, lib=None):
+              sm_scale=1.0, pages_per_split=0, out=None, stream=None, row_group=1, lib=None,
+              window=None):
     """Paged decode attention on torch device tensors; returns out [B][H][D] fp32.
     row_group > 1 uses the beam-aware schedule (pa_decode_grouped).  lib: the
-    library to call (default the product build; load_tune() for variant tests)."""
+    library to call (default the product build; load_tune() for variant tests).
+    window (not None): pa_decode_window, row b attends to its last `window` tokens."""
     import torch
     lib = lib or load()
     B, H, D = q.shape
@@ -348,7 +365,13 @@ def pa_decode(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_lens=N
     view = kv_view(k_pool, v_pool, page_table)
     ws_bytes = lib.pa_decode_workspace_bytes(B, H, D, page_table.shape[2], pages_per_split)
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=q.device)
-    if row_group > 1:
+    if window is not None:
+        if row_group > 1:
+            raise ValueError("pa_decode: a window needs row_group 1")
+        check(lib.pa_decode_window(ctypes.byref(view), ptr(q), ptr(out), ptr(beam_ids),
+                                   ptr(context_lens), B, H, D, T, sm_scale, pages_per_split,
+                                   window, ptr(ws), ws_bytes, stream_ptr(stream)), lib)
+    elif row_group > 1:
         check(lib.pa_decode_grouped(ctypes.byref(view), ptr(q), ptr(out), ptr(beam_ids),
                                     ptr(context_lens), B, H, D, T, sm_scale, pages_per_split,
                                     row_group, ptr(ws), ws_bytes, stream_ptr(stream)))
@@ -357,6 +380,23 @@ def pa_decode(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_lens=N
                             ptr(context_lens), B, H, D, T, sm_scale, pages_per_split, ptr(ws),
                             ws_bytes, stream_ptr(stream)))
     return out
+
+
+def pa_decode_plan(k_pool, v_pool, page_table, *, B, T, pages_per_split=0, row_group=1,
+                   window=None, lib=None):
+    """(nsplit, form) of the pa_decode / pa_decode_grouped call with these
+    arguments, or of pa_decode_window when window is not None."""
+    lib = lib or load()
+    view = kv_view(k_pool, v_pool, page_table)
+    H, D = page_table.shape[1], k_pool.shape[2]
+    ns, form = ctypes.c_int32(0), ctypes.c_int32(0)
+    if window is not None:
+        check(lib.pa_decode_window_plan(ctypes.byref(view), B, H, D, T, pages_per_split, window,
+                                        ctypes.byref(ns), ctypes.byref(form)), lib)
+    else:
+        check(lib.pa_decode_plan(ctypes.byref(view), B, H, D, T, pages_per_split, row_group,
+                                 ctypes.byref(ns), ctypes.byref(form)), lib)
+    return ns.value, form.value
 
 
 def pa_decode_ex(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_lens=None,
@@ -384,11 +424,12 @@ def pa_decode_ex(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_len
 
 
 def pa_prefill(q, k_pool, v_pool, page_table, *, row, p0, sm_scale=1.0, out=None,
-               split=True, stream=None):
+               split=True, stream=None, window=None):
     """Causal attention of a prompt chunk (pa_prefill): q [m][H][D] (or a
     [m][stride] row view whose first H*D floats are the heads) at positions
     p0 .. p0+m-1 of page-table row `row`; returns out [m][H][D] fp32.
-    split=False runs the one-pass form (no workspace)."""
+    split=False runs the one-pass form (no workspace).  window (not None):
+    pa_prefill_window, query i sees positions max(0, p0+i-window+1) .. p0+i."""
     import torch
     lib = load()
     m = q.shape[0]
@@ -401,6 +442,11 @@ def pa_prefill(q, k_pool, v_pool, page_table, *, row, p0, sm_scale=1.0, out=None
     view = kv_view(k_pool, v_pool, page_table)
     ws_bytes = lib.pa_prefill_workspace_bytes(ctypes.byref(view), p0, m) if split else 0
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=q.device) if ws_bytes else None
+    if window is not None:
+        check(lib.pa_prefill_window(ctypes.byref(view), ptr(q), q_stride, ptr(out), out.stride(0),
+                                    row, p0, m, sm_scale, window, ptr(ws), ws_bytes,
+                                    stream_ptr(stream)))
+        return out
     check(lib.pa_prefill(ctypes.byref(view), ptr(q), q_stride, ptr(out), out.stride(0), row, p0,
                          m, sm_scale, ptr(ws), ws_bytes, stream_ptr(stream)))
     return out
@@ -412,12 +458,13 @@ def prefill_segs(segs):
 
 
 def pa_prefill_packed(q, k_pool, v_pool, page_table, *, segs, sm_scale=1.0, out=None,
-                      split=True, stream=None):
+                      split=True, stream=None, window=None):
     """Causal attention of prompt chunks of several sequences in one launch
     (pa_prefill_packed): q [m][H][D] (or a [m][stride] row view whose first
     H*D floats are the heads), m = sum of the segment lengths, segs =
     [(row, p0, len), ...] in packed order; returns out [m][H][D] fp32.
-    split=False gives the workspace of the one-pass form."""
+    split=False gives the workspace of the one-pass form.  window (not None):
+    pa_prefill_packed_window."""
     import torch
     lib = load()
     m = q.shape[0]
@@ -433,6 +480,11 @@ def pa_prefill_packed(q, k_pool, v_pool, page_table, *, segs, sm_scale=1.0, out=
     ws_bytes = lib.pa_prefill_packed_workspace_bytes(ctypes.byref(view), arr, len(segs),
                                                      1 if split else 0)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    if window is not None:
+        check(lib.pa_prefill_packed_window(ctypes.byref(view), ptr(q), q.stride(0), ptr(out),
+                                           out.stride(0), arr, len(segs), sm_scale, window,
+                                           ptr(ws), ws_bytes, stream_ptr(stream)))
+        return out
     check(lib.pa_prefill_packed(ctypes.byref(view), ptr(q), q.stride(0), ptr(out), out.stride(0),
                                 arr, len(segs), sm_scale, ptr(ws), ws_bytes, stream_ptr(stream)))
     return out
@@ -544,6 +596,12 @@ def kv_cache_reorder(kv_handle, first_beam, parent, n_tokens) -> None:
     """kv_cache_reorder on a kv_cache handle (KVTileCache.handle, decoder.kv_handle)."""
     arr = (ctypes.c_int32 * len(parent))(*parent)
     check(load().kv_cache_reorder(c_void_p(kv_handle), first_beam, len(parent), arr, n_tokens))
+
+
+def kv_cache_release_before(kv_handle, beam, n_tokens) -> None:
+    """kv_cache_release_before on a kv_cache handle: the pages of `beam`'s tiles
+    wholly below token n_tokens go back to the pool, their entries read -1."""
+    check(load().kv_cache_release_before(c_void_p(kv_handle), beam, n_tokens))
 
 
 def quantize_rows(x, stream=None):

@@ -13,6 +13,11 @@ for a prompt chunk before pa_prefill read FP8 pools), in alternating blocks
 timed with device events; the medians and block-to-block spreads go to --out
 (default profiles/prefill_fp8.json, key "kernel_ab").
 
+--window W [W ...]: only time the (--p0, --m) chunk of C3's heads through
+pa_prefill_window at each W (0: off), alternating blocks as the A/B above; the
+medians, spreads and the algorithmic rate over the visible (query, key) pairs
+go to --out under "window" (profiles/prefill_window.json).
+
 --e2e N: only time `prefill` of an N-token prompt on a C3-dims INT8Decoder of
 --layers layers with KV pools of the (one) --kv-dtype, and store it in --out
 under "e2e"[--label] (run it once per library build on the same box, as
@@ -128,6 +133,32 @@ def kernel_ab(H, D, ts, p0, m, blocks=7, iters=10):
     return res
 
 
+def window_ab(H, D, ts, p0, m, windows, kv_dtype="fp16", blocks=7, iters=10):
+    """pa_prefill_window of one chunk at each window of `windows` (0: off), one
+    block of `iters` launches each in turn, `blocks` rounds.  Visible pairs of a
+    query at position p: min(p + 1, W)."""
+    import llm_capi
+    pools, pt, q, out, bi, cl = make_case(H, D, ts, p0, m, [kv_dtype])
+    kp, vp = pools[kv_dtype]
+    forms = {W: (lambda W=W: llm_capi.pa_prefill(q, kp, vp, pt, row=0, p0=p0, out=out, window=W))
+             for W in windows}
+    for fn in forms.values():
+        time_cuda(fn, 3)
+    times = {W: [] for W in windows}
+    for _ in range(blocks):
+        for W, fn in forms.items():
+            times[W].append(time_cuda(fn, iters))
+    res = {"H": H, "D": D, "page": ts, "p0": p0, "m": m, "kv_dtype": kv_dtype, "blocks": blocks,
+           "iters_per_block": iters, "arms": {}}
+    for W, ts_ in times.items():
+        pairs = sum(min(p + 1, W) if W > 0 else p + 1 for p in range(p0, p0 + m))
+        med = statistics.median(ts_)
+        res["arms"][str(W)] = {"median_us": round(med, 1), "spread_us": round(max(ts_) - min(ts_), 1),
+                               "blocks_us": [round(t, 1) for t in ts_], "visible_pairs": pairs,
+                               "TFLOPs_over_visible_pairs": round(4.0 * H * D * pairs / med / 1e6, 1)}
+    return res
+
+
 def decoder_bench(prompt, kv_dtype="fp16", layers=None):
     import llm_decoder
     from bench import CONFIGS, make_weights
@@ -169,6 +200,8 @@ def main():
     ap.add_argument("--kv-dtype", nargs="+", choices=["fp16", "fp8"], default=["fp16"],
                     help="KV pool type; both: the same-process FP8 / fp16 / decode-rows A/B")
     ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--window", type=int, nargs="+", default=None, metavar="W",
+                    help="only time the chunk through pa_prefill_window at each W (0: off)")
     ap.add_argument("--e2e", type=int, default=0, metavar="N",
                     help="only time prefill of an N-token prompt (C3 dims, --layers layers)")
     ap.add_argument("--layers", type=int, default=2)
@@ -181,6 +214,11 @@ def main():
     import torch
     torch.cuda.set_device(0)
     kvd = list(dict.fromkeys(args.kv_dtype))
+    if args.window is not None:
+        rec = window_ab(16, 128, 16, args.p0, args.m, args.window, kvd[0], blocks=args.blocks)
+        update_json(args.out, lambda d: d.__setitem__("window", rec))
+        print(json.dumps({"window": rec}), flush=True)
+        return
     if args.e2e:
         if len(kvd) != 1:
             ap.error("--e2e takes one --kv-dtype")
