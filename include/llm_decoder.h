@@ -350,6 +350,24 @@ int argmax_rows(const float* logits, int rows, int V, int32_t* out, void* stream
  * V <= 65536. */
 int sample_rows(const float* logits, int rows, int V, float temperature, int top_k, float top_p,
                 uint64_t seed, int counter, int32_t* out, void* stream);
+/* sample_rows with every row's own settings, for rows of different requests in
+ * one launch (the token choice of llm_decoder_serve_step): temperature /
+ * top_p fp32 [rows], top_k / counter int32 [rows], seed uint64 [rows], all
+ * DEVICE arrays read by the one launch (the same kernel as sample_rows: a
+ * workgroup handles one row, so the choice between the greedy and the
+ * sampling path is uniform within it).  Row r is greedy if temperature[r] <= 0
+ * or top_k[r] == 1 (first maximum wins); else it draws with
+ *   u = sample_uniform_host(seed[r], 0, counter[r]):
+ * the row term of the hash is 0, so a row's token depends on its logits, its
+ * settings, its seed and its counter, not on where it sits in the launch.
+ * Any array may be NULL: temperature 1, top_k 0 (off), top_p 1 (off),
+ * counter 0, and a NULL seed is sample_rows' draw, u = sample_uniform_host(0,
+ * r, counter) -- all NULL is sample_rows(logits, rows, V, 1, 0, 1, 0, 0, ..).
+ * The shape checks are sample_rows' (V <= 65536); the settings are device
+ * data and are not checked: top_k < 0 counts as 0, top_p >= 1 as off. */
+int sample_rows_each(const float* logits, int rows, int V, const float* temperature,
+                     const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                     const int32_t* counter, int32_t* out, void* stream);
 /* Beam candidates of one decode step (csrc/beam_select.hip).  logits fp32
  * [rows][V] device with rows = num_seqs * W, row = seq * W + beam, 1 <= W <= 4;
  * score_in fp32 [rows] device, a beam's cumulative log-probability, -inf for
@@ -725,6 +743,100 @@ int llm_decoder_packed_prefill(const llm_decoder* d);
  * counter of a row is its position, so runs are replayable for a seed). */
 int llm_decoder_set_sampling(llm_decoder* d, float temperature, int top_k, float top_p,
                              uint64_t seed);
+
+/* ------------------------------------------------------------------------ */
+/* Continuous batching (serving mode)                                        */
+/* ------------------------------------------------------------------------ */
+/* Requests are submitted at any time; each llm_decoder_serve_step admits
+ * waiting requests into free rows, prefills them, runs ONE decode step over
+ * all live rows and hands back one token per live request; a row whose request
+ * ended is retired at once and its pages return to the pool.  Policy
+ * (csrc/serve_plan.hpp):
+ *   pages   a request appends at most T = prompt_len + max_new_tokens - 1
+ *           positions (llm_decoder_generate's bound) and is charged
+ *           num_layers * num_heads * tiles pages while it lives, tiles =
+ *           ceil(T / page_size), on a windowed decoder min(tiles,
+ *           ceil((window + 512) / page_size) + 1) (llm_decoder_set_window);
+ *   admit   strict FIFO at the start of a step: the head of the queue enters
+ *           while a row is free and committed + need(head) <= num_pages; a
+ *           head that does not fit is not skipped.  So no step of an admitted
+ *           request returns LLM_ERR_OOM; nothing is preempted;
+ *   rows    live rows are dense, 0 .. live - 1: a new request takes row
+ *           `live`; after a step the finished rows retire in descending row
+ *           order, and a retired row that is not the last live row receives
+ *           the last one (a page-table re-parenting: no page is copied).  A
+ *           request's row therefore changes over its life; events carry ids;
+ *   finish  LLM_FINISH_EOS when the chosen token is the request's eos_token
+ *           (the token is delivered, as llm_decoder_beam_search counts it),
+ *           LLM_FINISH_LENGTH after max_new_tokens tokens; EOS wins.
+ * Every decoder mode but beams composes: both weight types, fp16 / LLM_FP8
+ * pages, rope, a sliding window, packed prefill.  Nothing outside serving
+ * mode changes. */
+#define LLM_FINISH_EOS 1
+#define LLM_FINISH_LENGTH 2
+typedef struct llm_request_options {
+  int max_new_tokens;            /* >= 1 */
+  int eos_token;                 /* -1: none */
+  float temperature; int top_k; float top_p;  /* as llm_decoder_set_sampling; greedy if temperature <= 0 or top_k == 1 */
+  uint64_t seed;
+} llm_request_options;
+typedef struct llm_serve_event {
+  long long id; int32_t token; int32_t index;  /* 0-based generated index */
+  int32_t row;                                 /* the row it held during this step */
+  int32_t finish;                              /* 0, LLM_FINISH_EOS, LLM_FINISH_LENGTH */
+} llm_serve_event;
+/* Enter serving mode: the cache and the rows are cleared (row_group 1), ids
+ * count up from 0 again.  LLM_ERR_UNSUPPORTED in beam mode or with
+ * vocab_size > 65536 (every row's token is chosen by sample_rows_each),
+ * LLM_ERR_INVALID if already serving or without weights.  While serving,
+ * llm_decoder_generate, _beam_search, _begin_synthetic, _begin_beams,
+ * _prefill, _prefill_rows, _step and the setters _set_sampling, _set_window,
+ * _set_rope, _set_kv_scales, _set_packed_prefill and _set_taps return
+ * LLM_ERR_INVALID. */
+int llm_decoder_serve_begin(llm_decoder* d);
+/* Leave serving mode: every request, waiting or live, is dropped without an
+ * event, the cache is cleared and no rows stay active (batch 0).
+ * LLM_ERR_INVALID if not serving. */
+int llm_decoder_serve_end(llm_decoder* d);
+/* Queue a request of n >= 1 prompt ids (host; copied); *id receives its id
+ * (64-bit, counting up from 0 per llm_decoder_serve_begin).  Launches nothing.
+ * LLM_ERR_INVALID, with nothing queued, for a token id or eos_token out of
+ * range, top_k < 0, top_p outside (0, 1], a temperature that is not finite,
+ * T > max_seq_len, or a need above the pool's num_pages. */
+int llm_decoder_submit(llm_decoder* d, const int32_t* prompt, int n,
+                       const llm_request_options* opt, long long* id);
+/* Drop a request: a waiting one leaves the queue, a live one is retired at
+ * once by the row move of a retirement (nothing is in flight between steps)
+ * and its pages return.  No event is emitted.  Unknown or finished id:
+ * LLM_ERR_INVALID. */
+int llm_decoder_cancel(llm_decoder* d, long long id);
+/* One serving step, in this order: (1) admit; (2) prefill prompt[:-1] of
+ * every newly admitted row (llm_decoder_prefill_rows' passes if packed
+ * prefill is on, else row by row -- as llm_decoder_generate; live rows wait
+ * for it); (3) one decode step of all live rows, fed the last prompt token
+ * (new rows) or the previous chosen id, so a request's first token is
+ * produced exactly as llm_decoder_generate produces it; every row's token is
+ * chosen on the device by ONE sample_rows_each launch over the rows' own
+ * settings, the draw counter being the row's position; (4) one event per live
+ * row, in ascending row order; (5) finished rows retire.  logits_dev (device,
+ * may be NULL) receives the step's fp32 logits, row r of the events at
+ * logits_dev + r * vocab_size.  events has room for cap >= max_batch entries;
+ * *n_events receives the count.  With nothing live and nothing admissible the
+ * call launches nothing and returns *n_events = 0.  The decoder keeps one
+ * instantiated step graph, as llm_decoder_step does: a step whose live-row
+ * count differs from the last one's re-instantiates it
+ * (llm_decoder_serve_stats counts these).
+ * LLM_ERR_RANGE as llm_decoder_generate: the events are complete.  After any
+ * other error of a step the rows are in no defined state: leave the mode
+ * with llm_decoder_serve_end. */
+int llm_decoder_serve_step(llm_decoder* d, float* logits_dev, llm_serve_event* events, int cap,
+                           int* n_events);
+/* *live / *waiting requests, *committed_pages (the sum of the live requests'
+ * needs) and *graph_instantiations (step graphs instantiated by serving
+ * steps since the decoder was created).  Any pointer may be
+ * NULL; valid outside serving mode too (0 live, 0 waiting). */
+int llm_decoder_serve_stats(const llm_decoder* d, int* live, int* waiting,
+                            long long* committed_pages, long long* graph_instantiations);
 
 /* Low-level stepping (bench / multi-GPU driver). */
 /* Start `batch` rows whose first context_len tokens are synthetic: every page

@@ -22,7 +22,10 @@
 // begin_synthetic / step for the bench, prefill(row, tokens) and its packed
 // form prefill_batch(rows, token_lists) (llm_decoder_prefill_rows) with the
 // read/write packed_prefill switch that generate* / beam_search* follow
-// (llm_decoder_set_packed_prefill, default False), PageTable / KVTileCache classes with
+// (llm_decoder_set_packed_prefill, default False), continuous batching
+// (serve_begin / submit / cancel / serve_step / serve_stats / serve_end over
+// llm_decoder_serve_*, and generate_many, the serve loop over any number of
+// prompts), PageTable / KVTileCache classes with
 // the kv_cache/ API names (page_table.hpp:5-37, kv_tile_cache.hpp:9-41) and
 // paged_attention() over raw device pointers.
 //
@@ -296,6 +299,97 @@ class Decoder {
   void set_sampling(float temperature, int top_k, float top_p, uint64_t seed) {
     py::gil_scoped_release nogil;
     check(llm_decoder_set_sampling(d_, temperature, top_k, top_p, seed));
+  }
+
+  // Continuous batching (llm_decoder_serve_*): submit at any time, one
+  // serve_step = admissions + their prefill + one decode step of all live rows
+  void serve_begin() {
+    py::gil_scoped_release nogil;
+    check(llm_decoder_serve_begin(d_));
+  }
+  void serve_end() {
+    py::gil_scoped_release nogil;
+    check(llm_decoder_serve_end(d_));
+  }
+  long long submit(const std::vector<int32_t>& tokens, int max_new_tokens, int eos_token_id,
+                   float temperature, int top_k, float top_p, uint64_t seed) {
+    llm_request_options o{max_new_tokens, eos_token_id, temperature, top_k, top_p, seed};
+    long long id = -1;
+    check(llm_decoder_submit(d_, tokens.data(), (int)tokens.size(), &o, &id));
+    return id;
+  }
+  void cancel(long long id) { check(llm_decoder_cancel(d_, id)); }
+  // [(id, token, index, row, finish), ...] of the step's live rows, ascending
+  // row; logits_ptr: device [max_batch][V] floats for the step's logits (0: none)
+  py::list serve_step(uintptr_t logits_ptr) {
+    std::vector<llm_serve_event> ev((size_t)std::max(cfg_.max_batch, 1));
+    int n = 0;
+    {
+      py::gil_scoped_release nogil;
+      check(llm_decoder_serve_step(d_, reinterpret_cast<float*>(logits_ptr), ev.data(),
+                                   (int)ev.size(), &n));
+    }
+    py::list res;
+    for (int i = 0; i < n; ++i)
+      res.append(py::make_tuple(ev[i].id, ev[i].token, ev[i].index, ev[i].row, ev[i].finish));
+    return res;
+  }
+  // {live, waiting, committed_pages, graph_instantiations}
+  py::dict serve_stats() const {
+    int live = 0, waiting = 0;
+    long long committed = 0, inst = 0;
+    check(llm_decoder_serve_stats(d_, &live, &waiting, &committed, &inst));
+    py::dict s;
+    s["live"] = live; s["waiting"] = waiting; s["committed_pages"] = committed;
+    s["graph_instantiations"] = inst;
+    return s;
+  }
+  // Any number of prompts through the serve loop: the generated ids per prompt
+  // in submission order (EOS included where hit).  max_new_tokens: one int or
+  // one per prompt; prompt i draws with seed + i.
+  std::vector<std::vector<int>> generate_many(const std::vector<std::vector<int32_t>>& prompts,
+                                              py::object max_new_tokens, int eos_token_id,
+                                              float temperature, int top_k, float top_p,
+                                              uint64_t seed) {
+    const size_t n = prompts.size();
+    std::vector<int> max_new;
+    if (py::isinstance<py::int_>(max_new_tokens)) max_new.assign(n, max_new_tokens.cast<int>());
+    else max_new = max_new_tokens.cast<std::vector<int>>();
+    if (max_new.size() != n)
+      throw std::invalid_argument("generate_many: max_new_tokens must be an int or one per prompt");
+    std::vector<std::vector<int>> out(n);
+    if (n == 0) return out;
+    std::vector<llm_serve_event> ev((size_t)std::max(cfg_.max_batch, 1));
+    py::gil_scoped_release nogil;
+    check(llm_decoder_serve_begin(d_));
+    int rc = LLM_OK, range_rc = LLM_OK;
+    for (size_t i = 0; i < n && rc == LLM_OK; ++i) {
+      llm_request_options o{max_new[i], eos_token_id, temperature, top_k, top_p, seed + i};
+      long long id = -1;
+      rc = llm_decoder_submit(d_, prompts[i].data(), (int)prompts[i].size(), &o, &id);
+    }
+    for (size_t left = n; rc == LLM_OK && left > 0;) {
+      int ne = 0;
+      rc = llm_decoder_serve_step(d_, nullptr, ev.data(), (int)ev.size(), &ne);
+      if (rc == LLM_ERR_RANGE) { range_rc = rc; rc = LLM_OK; }  // (ids complete, as generate)
+      if (rc == LLM_OK && ne == 0) {  // requests outstanding and nothing live or admissible
+        (void)llm_decoder_serve_end(d_);
+        throw std::runtime_error("llm_decoder: generate_many: a serve step returned no event "
+                                 "with requests outstanding");
+      }
+      for (int j = 0; j < ne; ++j) {
+        out[(size_t)ev[j].id].push_back(ev[j].token);
+        left -= ev[j].finish != 0;
+      }
+    }
+    std::string err = rc != LLM_OK ? llm_last_error() : "";
+    const int rc_end = llm_decoder_serve_end(d_);
+    if (rc != LLM_OK) throw std::runtime_error("llm_decoder: " + err);
+    check(rc_end);
+    if (range_rc)
+      throw std::runtime_error("llm_decoder: generate_many: the fused o_proj clamped a head "
+                               "product in at least one step");
+    return out;
   }
 
   void begin_beams(int num_seqs, int beam_width, int shared_len, int beam_len, uint64_t seed,
@@ -635,6 +729,18 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def_property("packed_prefill", &Decoder::packed_prefill, &Decoder::set_packed_prefill)
         .def("set_sampling", &Decoder::set_sampling, py::arg("temperature"),
              py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("seed") = 0)
+        .def("serve_begin", &Decoder::serve_begin)
+        .def("submit", &Decoder::submit, py::arg("tokens"), py::arg("max_new_tokens"),
+             py::arg("eos_token_id") = -1, py::arg("temperature") = 0.0f, py::arg("top_k") = 0,
+             py::arg("top_p") = 1.0f, py::arg("seed") = 0)
+        .def("cancel", &Decoder::cancel, py::arg("id"))
+        .def("serve_step", &Decoder::serve_step, py::arg("logits_ptr") = 0)
+        .def("serve_stats", &Decoder::serve_stats)
+        .def("serve_end", &Decoder::serve_end)
+        .def("generate_many", &Decoder::generate_many, py::arg("prompts"),
+             py::arg("max_new_tokens"), py::arg("eos_token_id") = -1,
+             py::arg("temperature") = 0.0f, py::arg("top_k") = 0, py::arg("top_p") = 1.0f,
+             py::arg("seed") = 0)
         .def("begin_beams", &Decoder::begin_beams, py::arg("num_seqs"), py::arg("beam_width"),
              py::arg("shared_len"), py::arg("beam_len"), py::arg("seed") = 0,
              py::arg("shuffle") = true)

@@ -43,6 +43,11 @@ hipError_t launch_argmax_partials(const float* part_val, const int32_t* part_idx
 hipError_t launch_sample(const float* logits, int rows, int row0, int V, float temperature,
                          int top_k, float top_p, uint64_t seed, const int32_t* counter,
                          int32_t* out, hipStream_t st);
+// launch_sample with each row's own settings (device [rows] each; a NULL array
+// takes sample_rows_each's default for it): the token choice of a serving step
+hipError_t launch_sample_each(const float* logits, int rows, int V, const float* temperature,
+                              const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                              const int32_t* counter, int32_t* out, hipStream_t st);
 // Beam candidates (csrc/beam_select.hip, beam_select_rows in llm_decoder.h):
 // the row stage and the merge stage on `st`, both capturable.  ws: device
 // scratch of beam_select_ws_floats(num_seqs, W) floats (the row stage's

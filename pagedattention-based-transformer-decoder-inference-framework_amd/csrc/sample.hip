@@ -55,6 +55,15 @@ struct SampleArgs {
   int32_t* out;
   int32_t* out2;  // optional second destination (stride out2_stride)
   int out2_stride;
+  // Optional per-row settings (device [rows]; NULL -> the scalar above), for
+  // rows of different requests in one launch (continuous batching).  With
+  // seed_v the draw's row term is 0: u = sample_uniform(seed_v[r], 0, counter),
+  // so a request's draws depend on its seed and counter only, whichever row it
+  // holds.
+  const float* temperature_v;
+  const int32_t* top_k_v;
+  const float* top_p_v;
+  const uint64_t* seed_v;
 };
 
 template <int VPT>
@@ -68,7 +77,11 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(SampleArgs 
   const int base = threadIdx.x * VPT;
   RowVals<VPT> p;
   p.lds = spill;
-  const bool greedy = a.temperature <= 0.f || a.top_k == 1;
+  // the row's settings: uniform over the workgroup (one workgroup per row)
+  const float temperature = a.temperature_v ? a.temperature_v[r] : a.temperature;
+  const int top_k = a.top_k_v ? a.top_k_v[r] : a.top_k;
+  const float top_p = a.top_p_v ? a.top_p_v[r] : a.top_p;
+  const bool greedy = temperature <= 0.f || top_k == 1;
   p.each([&](int i, float& v) { v = base + i < a.V ? lg[base + i] : -INFINITY; });
 
   if (greedy) {
@@ -91,7 +104,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(SampleArgs 
   // temperature + softmax (reference: logits /= T; exp(x - max); / (sum + 1e-6))
   float mloc = -INFINITY;
   p.each([&](int, float& v) {
-    v = v / a.temperature;
+    v = v / temperature;
     mloc = fmaxf(mloc, v);
   });
   const float m = block_reduce(mloc, shf, [](float x, float y) { return fmaxf(x, y); });
@@ -106,29 +119,29 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(SampleArgs 
 
   // top-k: bit pattern of the k-th largest probability (keep bits >= tk)
   uint32_t tk = 0;
-  if (a.top_k > 0 && a.top_k < a.V) {
+  if (top_k > 0 && top_k < a.V) {
     for (int bit = 30; bit >= 0; --bit) {
       const uint32_t cand = tk | (1u << bit);
       uint32_t c = 0;
       p.each([&](int, float& v) { c += __float_as_uint(v) >= cand; });
       c = block_reduce(c, shu, [](uint32_t x, uint32_t y) { return x + y; });
-      if (c >= (uint32_t)a.top_k) tk = cand;
+      if (c >= (uint32_t)top_k) tk = cand;
     }
   }
   // top-p: keep p_i iff the mass strictly above it is < top_p, i.e. bits > tp
   // where tp is the largest pattern whose strictly-above mass is >= top_p
   int64_t tp = -1;
-  if (a.top_p < 1.0f) {
+  if (top_p < 1.0f) {
     auto mass_above = [&](uint32_t t) {
       float ms = 0.f;
       p.each([&](int, float& v) { ms += __float_as_uint(v) > t ? v : 0.f; });
       return block_reduce(ms, shf, [](float x, float y) { return x + y; });
     };
-    if (mass_above(0u) >= a.top_p) {
+    if (mass_above(0u) >= top_p) {
       uint32_t t = 0;
       for (int bit = 30; bit >= 0; --bit) {
         const uint32_t cand = t | (1u << bit);
-        if (mass_above(cand) >= a.top_p) t = cand;
+        if (mass_above(cand) >= top_p) t = cand;
       }
       tp = t;
     }
@@ -152,7 +165,8 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(SampleArgs 
   }
   const float Z = scan[kSampleThreads - 1];
   const int ctr = a.counter ? a.counter[r] : a.counter0;
-  const float target = sample_uniform(a.seed, a.row0 + r, ctr) * Z;
+  const float target = (a.seed_v ? sample_uniform(a.seed_v[r], 0, ctr)
+                                 : sample_uniform(a.seed, a.row0 + r, ctr)) * Z;
   const float lo = threadIdx.x ? scan[threadIdx.x - 1] : 0.f;
   // The claims must tile [0, Z).  `lo + part` is one fp32 add and the next
   // thread's lo another association of the same terms, an ulp apart often
@@ -229,6 +243,28 @@ hipError_t llm::launch_sample(const float* logits, int rows, int row0, int V, fl
                               int32_t* out, hipStream_t st) {
   SampleArgs a{logits, V, temperature, top_k, top_p, seed, counter, 0, row0, out, nullptr, 0};
   return launch_sample_rows(a, rows, st);
+}
+
+hipError_t llm::launch_sample_each(const float* logits, int rows, int V, const float* temperature,
+                                   const int32_t* top_k, const float* top_p,
+                                   const uint64_t* seed, const int32_t* counter, int32_t* out,
+                                   hipStream_t st) {
+  // (the scalars are what a NULL array stands for: sample_rows' plain draw)
+  SampleArgs a{logits, V, 1.0f, 0, 1.0f, 0, counter, 0, 0, out, nullptr, 0,
+               temperature, top_k, top_p, seed};
+  return launch_sample_rows(a, rows, st);
+}
+
+extern "C" int sample_rows_each(const float* logits, int rows, int V, const float* temperature,
+                                const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                                const int32_t* counter, int32_t* out, void* stream) {
+  LLM_REQUIRE(rows >= 0 && V > 0, "sample_rows_each: bad shape");
+  if (rows == 0) return LLM_OK;
+  LLM_REQUIRE(logits && out, "sample_rows_each: NULL pointer");
+  LLM_REQUIRE(V <= 128 * kSampleThreads, "sample_rows_each: V > 65536");
+  LLM_HIP_RET(launch_sample_each(logits, rows, V, temperature, top_k, top_p, seed, counter, out,
+                                 as_stream(stream)));
+  return LLM_OK;
 }
 
 extern "C" float sample_uniform_host(uint64_t seed, int row, int counter) {

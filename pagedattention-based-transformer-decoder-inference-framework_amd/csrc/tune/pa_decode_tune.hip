@@ -6,12 +6,14 @@
 // routes a beam-group launch to the experiment switched on), the pa_decode_tune
 // A/B entry of the split kernel's register-stage / cache-policy variants
 // (scripts/bench_kernels.py, scripts/tune_attention.py; each variant is the
-// PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry, and
-// prefill_passes_tune, the prefill pass packer's.
+// PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry,
+// prefill_passes_tune, the prefill pass packer's, and serve_plan_sim_tune, the
+// continuous-batching scheduler's.
 #include "tune/pa_decode_tune.hpp"
 #include "tune/pa_beam_steal.hpp"
 #include "pa_tuning.hpp"
 #include "prefill_pack.hpp"
+#include "serve_plan.hpp"
 
 namespace llm {
 
@@ -1062,6 +1064,72 @@ extern "C" int prefill_passes_tune(const int32_t* start, const int32_t* len, int
     ++pi;
   }
   return n;
+}
+
+// Tuning hook: the continuous-batching scheduler (serve_plan.hpp) run on
+// explicit requests without a device, so a test reads the row decisions
+// llm_decoder_serve_step executes.  All n requests (prompt_lens[i], max_new[i];
+// ids 0 .. n-1) are submitted before step 1; request i ends after gen_lens[i]
+// tokens (1 .. max_new[i]).  Steps count from 1 and stop when nothing is live
+// or waiting.  out: int64 records (step, kind, id, row, aux), the first `room`
+// of them, in the order a serve step produces them:
+//   kind 0 admit   row = the row taken, aux = pages committed after it
+//   kind 1 token   row = the row held during the step, aux = generated index
+//   kind 2 move    row = the destination row, aux = the source row
+//   kind 3 retire  row = the row given up, aux = 1 (ended before max_new, as
+//                  an EOS would) or 2 (max_new tokens delivered)
+// Returns the record count, -1 if a request is refused (T > max_seq_len or a
+// need above num_pages), -(count) if `room` is too small (out then holds the
+// first `room` records), INT_MIN on bad arguments.
+extern "C" int serve_plan_sim_tune(const int32_t* prompt_lens, const int32_t* max_new,
+                                   const int32_t* gen_lens, int n, int max_rows,
+                                   long long num_pages, int pages_per_tile, int page_size,
+                                   int window, int max_seq_len, long long* out, int room) {
+  constexpr int kBad = -2147483647 - 1;
+  if (n < 0 || max_rows < 1 || num_pages < 1 || pages_per_tile < 1 || page_size < 1 ||
+      window < 0 || max_seq_len < 1 || room < 0 || (room && !out) ||
+      (n && (!prompt_lens || !max_new || !gen_lens)))
+    return kBad;
+  for (int i = 0; i < n; ++i)
+    if (prompt_lens[i] < 1 || max_new[i] < 1 || gen_lens[i] < 1 || gen_lens[i] > max_new[i])
+      return kBad;
+  ServeGeom g;
+  g.max_rows = max_rows; g.num_pages = num_pages; g.pages_per_tile = pages_per_tile;
+  g.page_size = page_size; g.window = window; g.max_seq_len = max_seq_len;
+  ServePlan plan;
+  plan.begin(g);
+  for (int i = 0; i < n; ++i)
+    if (plan.submit(prompt_lens[i], max_new[i]) != i) return -1;
+  long long count = 0;
+  auto rec = [&](long long step, long long kind, long long id, long long row, long long aux) {
+    if (count < room) {
+      long long* q = out + 5 * count;
+      q[0] = step, q[1] = kind, q[2] = id, q[3] = row, q[4] = aux;
+    }
+    ++count;
+  };
+  for (long long step = 1; plan.live() + plan.waiting() > 0; ++step) {
+    const int before = plan.live(), na = plan.admit();
+    long long committed = plan.committed();
+    for (int r = before + na - 1; r >= before; --r) committed -= plan.row(r).need;
+    for (int r = before; r < before + na; ++r) {
+      committed += plan.row(r).need;
+      rec(step, 0, plan.row(r).id, r, committed);
+    }
+    if (plan.live() == 0) return kBad;  // (not reached: a lone request always fits)
+    plan.finish_step(
+        [&](int r, const ServeReq& q) {
+          rec(step, 1, q.id, r, q.delivered);
+          return q.delivered + 1 == gen_lens[q.id] && gen_lens[q.id] < q.max_new;
+        },
+        [&](int r, const ServeReq& q, int finish, const ServeMove* mv) {
+          rec(step, 3, q.id, r, finish);
+          if (mv) rec(step, 2, plan.row(mv->dst).id, mv->dst, mv->src);
+          return 0;
+        });
+  }
+  if (count > 2147483647LL) return kBad;
+  return count > room ? -(int)count : (int)count;
 }
 
 // Tuning hook (not part of include/llm_decoder.h): run the split kernel of

@@ -82,6 +82,22 @@ class LlmBeamOptions(ctypes.Structure):
                 ("steps_run", ctypes.POINTER(ctypes.c_int))]
 
 
+LLM_FINISH_EOS, LLM_FINISH_LENGTH = 1, 2
+
+
+class LlmRequestOptions(ctypes.Structure):
+    """llm_request_options of llm_decoder_submit."""
+    _fields_ = [("max_new_tokens", ctypes.c_int), ("eos_token", ctypes.c_int),
+                ("temperature", ctypes.c_float), ("top_k", ctypes.c_int),
+                ("top_p", ctypes.c_float), ("seed", ctypes.c_uint64)]
+
+
+class LlmServeEvent(ctypes.Structure):
+    """llm_serve_event of llm_decoder_serve_step."""
+    _fields_ = [("id", ctypes.c_longlong), ("token", ctypes.c_int32), ("index", ctypes.c_int32),
+                ("row", ctypes.c_int32), ("finish", ctypes.c_int32)]
+
+
 class LlmError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"[llm status {status}] {msg}")
@@ -160,7 +176,22 @@ _SIGS = {
     "argmax_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sample_rows": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, ctypes.c_uint64,
                             c_int, c_void_p, c_void_p]),
+    "sample_rows_each": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
     "sample_uniform_host": (c_float, [ctypes.c_uint64, c_int, c_int]),
+    # continuous batching (llm_decoder_serve_*)
+    "llm_decoder_serve_begin": (c_int, [c_void_p]),
+    "llm_decoder_serve_end": (c_int, [c_void_p]),
+    "llm_decoder_submit": (c_int, [c_void_p, c_i32p, c_int, ctypes.POINTER(LlmRequestOptions),
+                                   ctypes.POINTER(c_ll)]),
+    "llm_decoder_cancel": (c_int, [c_void_p, c_ll]),
+    "llm_decoder_serve_step": (c_int, [c_void_p, c_void_p, ctypes.POINTER(LlmServeEvent), c_int,
+                                       ctypes.POINTER(c_int)]),
+    "llm_decoder_serve_stats": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                        ctypes.POINTER(c_ll), ctypes.POINTER(c_ll)]),
+    # tuning library only: the continuous-batching scheduler (csrc/serve_plan.hpp)
+    "serve_plan_sim_tune": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_ll, c_int, c_int,
+                                    c_int, c_int, ctypes.POINTER(c_ll), c_int]),
     "beam_select_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     "kv_cache_reorder": (c_int, [c_void_p, c_int, c_int, c_i32p, c_int]),
@@ -572,6 +603,45 @@ def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0, 
     check(lib.sample_rows(ptr(logits), R, V, temperature, top_k, top_p, seed, counter, ptr(out),
                           stream_ptr(stream)))
     return out
+
+
+def sample_rows_each(logits, temperature=None, top_k=None, top_p=None, seed=None, counter=None,
+                     stream=None):
+    """sample_rows_each on torch device tensors: fp32 logits [R][V] and per-row
+    device arrays (temperature / top_p float32, top_k / counter int32, seed
+    int64 holding the uint64 bits; None: the entry's default) -> int32 [R]."""
+    import torch
+    lib = load()
+    R, V = logits.shape
+    out = torch.empty(R, dtype=torch.int32, device=logits.device)
+    check(lib.sample_rows_each(ptr(logits), R, V, ptr(temperature), ptr(top_k), ptr(top_p),
+                               ptr(seed), ptr(counter), ptr(out), stream_ptr(stream)))
+    return out
+
+
+SERVE_ADMIT, SERVE_TOKEN, SERVE_MOVE, SERVE_RETIRE = range(4)
+
+
+def serve_plan_sim(prompt_lens, max_new, gen_lens, *, max_rows, num_pages, pages_per_tile,
+                   page_size, window=0, max_seq_len):
+    """serve_plan_sim_tune (tuning library): the records (step, kind, id, row,
+    aux) of a serving run in which every request is submitted before step 1
+    and request i ends after gen_lens[i] tokens; None if a request is refused."""
+    tune = load_tune()
+    n = len(prompt_lens)
+    arr = ctypes.c_int32 * max(n, 1)
+    args = (arr(*prompt_lens), arr(*max_new), arr(*gen_lens), n, max_rows, num_pages,
+            pages_per_tile, page_size, window, max_seq_len)
+    count = tune.serve_plan_sim_tune(*args, None, 0)
+    if count == -1:
+        return None
+    if count == -2 ** 31:
+        raise ValueError("serve_plan_sim: bad arguments")
+    room = abs(count)
+    out = (c_ll * (5 * max(room, 1)))()
+    got = tune.serve_plan_sim_tune(*args, out, room)
+    assert got == room, (got, room)
+    return [tuple(out[5 * i:5 * i + 5]) for i in range(room)]
 
 
 def beam_select(logits, score_in, W, stream=None):
