@@ -779,7 +779,8 @@ inline bool narrow_tile_for(int M, int N, int K, TileChoice& t) {
   }
   return false;
 }
-// fc2 as two k slices at 33..64 rows (decoder.cpp fc2_split: C5's K 16384):
+// fc2 as two k slices at 33..64 rows (decoder_step.cpp fc2_split: C5's K
+// 16384):
 // 2 column tiles x 64 rows x 8 waves per slice, 128 x 2 = 256 workgroups in
 // one round, each reading half of A (512 KB instead of the 1-tile form's
 // 1 MB per workgroup).  Same box, C5 (profiles/r06/c5_fc2_k2_ab.txt):

@@ -265,7 +265,7 @@ long long beam_resident_waves() {
 }  // namespace
 
 
-// The FP16 decoder's o_proj fused into the workgroup merge (decoder.cpp
+// The FP16 decoder's o_proj fused into the workgroup merge (decoder_step.cpp
 // oproj_fusable); LLM_OPROJ_FUSE=0 (tuning build) restores the o_proj GEMM.
 bool oproj_fuse_on() { return pa_tuning().oproj_fuse; }
 bool beam_steal_on() { return pa_tuning().beam_steal; }

@@ -1,7 +1,7 @@
 // Chunked prefill: the pass packer.  Host-only and pure (no HIP headers, no
 // decoder state): the prompts of some rows in, the layer passes that prefill
-// them out (decoder.cpp prefill_run runs them; prefill_passes_tune is the
-// test entry).
+// them out (decoder_prefill.cpp prefill_run runs them; prefill_passes_tune is
+// the test entry).
 #pragma once
 
 #include <algorithm>

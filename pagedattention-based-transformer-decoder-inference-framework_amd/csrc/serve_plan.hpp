@@ -1,6 +1,6 @@
 // Continuous batching: the scheduler core.  Host-only and pure (no HIP
 // headers, no decoder state): requests in, the row decisions of every serve
-// step out (decoder.cpp llm_decoder_serve_step executes them;
+// step out (decoder_serve.cpp llm_decoder_serve_step executes them;
 // serve_plan_sim_tune is the test entry).
 //
 // Policy, fixed here:

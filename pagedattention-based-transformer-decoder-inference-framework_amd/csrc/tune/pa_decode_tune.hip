@@ -7,10 +7,14 @@
 // A/B entry of the split kernel's register-stage / cache-policy variants
 // (scripts/bench_kernels.py, scripts/tune_attention.py; each variant is the
 // PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry,
-// prefill_passes_tune, the prefill pass packer's, and serve_plan_sim_tune, the
-// continuous-batching scheduler's.
+// prefill_passes_tune, the prefill pass packer's, serve_plan_sim_tune, the
+// continuous-batching scheduler's, and beam_book_tune, the beam search
+// bookkeeping's.
+#include <cmath>
+
 #include "tune/pa_decode_tune.hpp"
 #include "tune/pa_beam_steal.hpp"
+#include "beam_plan.hpp"
 #include "pa_tuning.hpp"
 #include "prefill_pack.hpp"
 #include "serve_plan.hpp"
@@ -1130,6 +1134,46 @@ extern "C" int serve_plan_sim_tune(const int32_t* prompt_lens, const int32_t* ma
   }
   if (count > 2147483647LL) return kBad;
   return count > room ? -(int)count : (int)count;
+}
+
+// Tuning hook: the beam search's host bookkeeping (beam_plan.hpp) run on
+// explicit candidates without a device, as llm_decoder_beam_search runs it on
+// the device's: cand_* [steps][num_seqs][2W] in rank order, min(max_new,
+// steps) steps or until every sequence is done.  out_ids [num_seqs][W]
+// [max_new], out_len / out_sum_logprob / out_score [num_seqs][W], live_parent
+// / live_token [steps][num_seqs][W] (the steps run are written), *steps_run.
+// Returns LLM_OK, LLM_ERR_INVALID on bad arguments, or the search's
+// LLM_ERR_HIP with its text when the candidates are refused.
+extern "C" int beam_book_tune(const float* cand_score, const int32_t* cand_parent,
+                              const int32_t* cand_token, int steps, int num_seqs, int W, int V,
+                              int max_new, int eos_token, float length_penalty, int32_t* out_ids,
+                              int32_t* out_len, float* out_sum_logprob, float* out_score,
+                              int32_t* live_parent, int32_t* live_token, int32_t* steps_run) {
+  LLM_REQUIRE(cand_score && cand_parent && cand_token && out_ids && out_len && out_sum_logprob &&
+                  out_score && live_parent && live_token && steps_run,
+              "beam_book_tune: NULL");
+  LLM_REQUIRE(W >= 1 && W <= 4 && V >= 2 * W, "beam_book_tune: W must be in [1, 4], V >= 2W");
+  LLM_REQUIRE(steps >= 1 && num_seqs >= 1 && max_new >= 1 && eos_token >= -1 && eos_token < V &&
+                  length_penalty >= 0.f && std::isfinite(length_penalty),
+              "beam_book_tune: steps, num_seqs, max_new >= 1; eos_token -1 or a token id; "
+              "length_penalty finite and >= 0");
+  BeamPlan plan;
+  plan.begin(num_seqs, W, max_new, eos_token, length_penalty, V);
+  const int K = 2 * W;
+  std::vector<float> score(W);
+  *steps_run = 0;
+  for (int st = 0; st < std::min(max_new, steps); ++st) {
+    for (int s = 0; s < num_seqs; ++s) {
+      const size_t c0 = ((size_t)st * num_seqs + s) * K, l0 = ((size_t)st * num_seqs + s) * W;
+      if (const char* err = plan.step(s, cand_score + c0, cand_parent + c0, cand_token + c0,
+                                      live_parent + l0, live_token + l0, score.data()))
+        return fail(LLM_ERR_HIP, err);
+    }
+    *steps_run = st + 1;
+    if (plan.all_done()) break;
+  }
+  plan.finish(out_ids, out_len, out_sum_logprob, out_score);
+  return LLM_OK;
 }
 
 // Tuning hook (not part of include/llm_decoder.h): run the split kernel of

@@ -192,6 +192,9 @@ _SIGS = {
     # tuning library only: the continuous-batching scheduler (csrc/serve_plan.hpp)
     "serve_plan_sim_tune": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_ll, c_int, c_int,
                                     c_int, c_int, ctypes.POINTER(c_ll), c_int]),
+    # tuning library only: the beam search's host bookkeeping (csrc/beam_plan.hpp)
+    "beam_book_tune": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float] +
+                       [c_void_p] * 7),
     "beam_select_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     "kv_cache_reorder": (c_int, [c_void_p, c_int, c_int, c_i32p, c_int]),
@@ -642,6 +645,36 @@ def serve_plan_sim(prompt_lens, max_new, gen_lens, *, max_rows, num_pages, pages
     got = tune.serve_plan_sim_tune(*args, out, room)
     assert got == room, (got, room)
     return [tuple(out[5 * i:5 * i + 5]) for i in range(room)]
+
+
+def beam_book(cand_score, cand_parent, cand_token, W, V, max_new, eos_token, length_penalty):
+    """beam_book_tune (tuning library): llm_decoder_beam_search's host
+    bookkeeping on candidate arrays [steps][num_seqs][2W] (float32, int32,
+    int32).  Returns (status, dict) with ids [S][W][max_new], length,
+    sum_logprob, score [S][W], live_parent / live_token [steps_run][S][W] and
+    steps; the dict is None unless the status is LLM_OK."""
+    import numpy as np
+    tune = load_tune()
+    cs = np.ascontiguousarray(cand_score, np.float32)
+    cp = np.ascontiguousarray(cand_parent, np.int32)
+    ct = np.ascontiguousarray(cand_token, np.int32)
+    steps, S, K = cs.shape
+    assert cp.shape == cs.shape == ct.shape
+    ids = np.zeros((S, W, max_new), np.int32)
+    length = np.zeros((S, W), np.int32)
+    sums, score = np.zeros((S, W), np.float32), np.zeros((S, W), np.float32)
+    lp = np.zeros((steps, S, W), np.int32)
+    lt = np.zeros_like(lp)
+    run = np.zeros(1, np.int32)
+    p = lambda a: a.ctypes.data_as(c_void_p)
+    rc = tune.beam_book_tune(p(cs), p(cp), p(ct), steps, S, W, V, max_new, eos_token,
+                             length_penalty, p(ids), p(length), p(sums), p(score), p(lp), p(lt),
+                             p(run))
+    if rc != LLM_OK:
+        return rc, None
+    n = int(run[0])
+    return rc, dict(ids=ids, length=length, sum_logprob=sums, score=score, live_parent=lp[:n],
+                    live_token=lt[:n], steps=n)
 
 
 def beam_select(logits, score_in, W, stream=None):
