@@ -113,6 +113,7 @@ int pa_merge_splits_internal(const float* part_acc, const float* part_ml, float*
 // workgroups and merged by pa_merge_rows_internal, which also writes `rows`
 // (the o_proj input); without, one pass writes out and `rows` is converted by
 // the row quantiser.  `out` may be NULL only when it splits and rows is set.
+// The split form is refused for H*D > 16384 (the merge's LDS row).
 // window > 0: query i attends to positions max(0, p0 + i - window + 1) .. p0 + i.
 bool pa_prefill_supported(const pa_kv_view* kv);
 size_t pa_prefill_ws_bytes(const pa_kv_view* kv, int p0, int m);
@@ -135,6 +136,15 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
                                const int32_t* ctx_dev, int m, int maxend, float sm_scale,
                                void* part_ws, size_t part_bytes, hipStream_t st,
                                const PaRowOutputs* rows = nullptr, int window = 0);
+// The same from a host segment list, as the C entry takes it: the list is
+// checked, the tile table and the contexts are written on the device into the
+// first pa_prefill_packed_meta_bytes of `workspace`, and what follows them is
+// the split workspace (part_ws above).
+int pa_prefill_packed_segs_internal(const pa_kv_view* kv, const float* q, int q_stride, float* out,
+                                    int out_stride, const pa_prefill_seg* segs, int nseg,
+                                    float sm_scale, int window, void* workspace,
+                                    size_t workspace_bytes, hipStream_t st,
+                                    const PaRowOutputs* rows = nullptr);
 
 // Bytes from page p to page p + 1 of a view's pools (page_stride 0 = dense).
 inline size_t kv_view_page_stride(const pa_kv_view& v) {

@@ -464,6 +464,9 @@ int pa_prefill_internal(const pa_kv_view* kv, const float* q, int q_stride, floa
                      (out == nullptr || out_stride == hid) &&
                      (!row_out || rows->pack);  // the merge writes packed o_proj inputs
   LLM_REQUIRE(out || (split && row_out), "pa_prefill: out is NULL");
+  // (the split merge holds a whole row in LDS, as pa_decode's row outputs)
+  LLM_REQUIRE(!split || (size_t)hid * 4 <= 65536,
+              "pa_prefill: the split form needs H*D <= 16384 (pass no workspace: one pass)");
   PaPrefillArgs a{};
   a.q = q;
   a.q_stride = q_stride;
@@ -631,6 +634,9 @@ int pa_prefill_packed_internal(const pa_kv_view* kv, const float* q, int q_strid
                      (out == nullptr || out_stride == hid) &&
                      (!row_out || rows->pack);  // the merge writes packed o_proj inputs
   LLM_REQUIRE(out || (split && row_out), "pa_prefill_packed: out is NULL");
+  LLM_REQUIRE(!split || (size_t)hid * 4 <= 65536,
+              "pa_prefill_packed: the split form needs H*D <= 16384 (pass no split workspace: "
+              "one pass)");
   PaPrefillArgs a{};
   a.q = q;
   a.q_stride = q_stride;
@@ -715,12 +721,12 @@ extern "C" int pa_prefill_packed(const pa_kv_view* kv, const float* q, int q_str
                                   workspace, workspace_bytes, stream);
 }
 
-extern "C" int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, int q_stride,
-                                        float* out, int out_stride, const pa_prefill_seg* segs,
-                                        int nseg, float sm_scale, int window, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  using namespace llm;
-  LLM_REQUIRE(kv && q && out, "pa_prefill_packed: NULL argument");
+int llm::pa_prefill_packed_segs_internal(const pa_kv_view* kv, const float* q, int q_stride,
+                                         float* out, int out_stride, const pa_prefill_seg* segs,
+                                         int nseg, float sm_scale, int window, void* workspace,
+                                         size_t workspace_bytes, hipStream_t st,
+                                         const PaRowOutputs* rows) {
+  LLM_REQUIRE(kv && q, "pa_prefill_packed: NULL argument");
   LLM_REQUIRE(window >= 0, "pa_prefill_packed: window must be >= 0 (0: off)");
   PackedShape ps;
   const int rc = packed_shape(kv, segs, nseg, &ps);
@@ -740,7 +746,6 @@ extern "C" int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, in
                   reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
               "pa_prefill_packed: workspace smaller than pa_prefill_packed_workspace_bytes(.., 0) "
               "or not 16-byte aligned");
-  hipStream_t st = as_stream(stream);
   int32_t* tiles = static_cast<int32_t*>(workspace);
   int32_t* ctx = tiles + (size_t)4 * ps.ntile;
   PackedMetaArgs ma{};
@@ -761,7 +766,17 @@ extern "C" int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, in
   }
   return pa_prefill_packed_internal(kv, q, qs, out, os, tiles, ps.ntile, ctx, ps.m, ps.maxend,
                                     sm_scale, static_cast<uint8_t*>(workspace) + meta,
-                                    workspace_bytes - meta, st, nullptr, window);
+                                    workspace_bytes - meta, st, rows, window);
+}
+
+extern "C" int pa_prefill_packed_window(const pa_kv_view* kv, const float* q, int q_stride,
+                                        float* out, int out_stride, const pa_prefill_seg* segs,
+                                        int nseg, float sm_scale, int window, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  LLM_REQUIRE(kv && q && out, "pa_prefill_packed: NULL argument");
+  return llm::pa_prefill_packed_segs_internal(kv, q, q_stride, out, out_stride, segs, nseg,
+                                              sm_scale, window, workspace, workspace_bytes,
+                                              llm::as_stream(stream));
 }
 
 extern "C" size_t pa_prefill_workspace_bytes(const pa_kv_view* kv, int p0, int m) {

@@ -8,8 +8,9 @@
 // (scripts/bench_kernels.py, scripts/tune_attention.py; each variant is the
 // PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry,
 // prefill_passes_tune, the prefill pass packer's, serve_plan_sim_tune, the
-// continuous-batching scheduler's, and beam_book_tune, the beam search
-// bookkeeping's.
+// continuous-batching scheduler's, beam_book_tune, the beam search
+// bookkeeping's, and pa_rows_tune, the internal attention entries with their
+// row outputs.
 #include <cmath>
 
 #include "tune/pa_decode_tune.hpp"
@@ -1174,6 +1175,82 @@ extern "C" int beam_book_tune(const float* cand_score, const int32_t* cand_paren
   }
   plan.finish(out_ids, out_len, out_sum_logprob, out_score);
   return LLM_OK;
+}
+
+// Tuning hook: the three internal attention entries (pa_decode_internal,
+// pa_prefill_internal, pa_prefill_packed_segs_internal) unchanged behind a
+// plain-C struct, so tests reach what the decoder's layers get back -- the
+// PaRowOutputs conversions of every launch form -- on shapes of their own
+// (ctypes mirror: llm_capi.PaRowsTuneArgs; tests/test_pa_rows_gpu.py).
+// No kernel code here.
+struct PaRowsTuneArgs {
+  int launch;  // 0 pa_decode_internal, 1 pa_prefill_internal, 2 the packed prefill
+  const pa_kv_view* kv;
+  const float* q;
+  int q_stride;
+  float sm_scale;
+  int window;
+  void* workspace;
+  size_t workspace_bytes;
+  // decode
+  const int32_t* beam_ids;
+  const int32_t* context_lens;
+  int B, H, D, T, pages_per_split, row_group;
+  int out_kind;  // PaOut: 1 ROW_Q, 2 ROW_F16, 3 F32_ROWS (0 F32; OPROJ is not reached here)
+  // prefill: positions p0 .. p0 + m - 1 of page-table row `row`
+  int row, p0, m;
+  // packed prefill: the segment list (host); the workspace starts with
+  // pa_prefill_packed_meta_bytes for the tile table and the contexts
+  const pa_prefill_seg* segs;
+  int nseg;
+  // PaRowOutputs (has_rows 0: the entry gets rows = NULL) and the fp32 out
+  int has_rows;
+  int8_t* rows_q;
+  float* inv_scale;
+  void* out16;
+  int pack, keep_out;
+  float out_scale;
+  float* out;
+  int out_stride;  // prefill entries (0: H*D)
+  // decode: the launch that ran (written before it runs; 0 / 0 if refused before the plan)
+  int nsplit, form;
+};
+
+extern "C" int pa_rows_tune(PaRowsTuneArgs* t, void* stream) {
+  LLM_REQUIRE(t, "pa_rows_tune: NULL arguments");
+  LLM_REQUIRE(t->launch >= 0 && t->launch <= 2, "pa_rows_tune: launch must be 0, 1 or 2");
+  t->nsplit = t->form = 0;
+  PaRowOutputs ro;
+  ro.q = t->rows_q;
+  ro.inv_scale = t->inv_scale;
+  ro.out16 = t->out16;
+  ro.pack = t->pack;
+  ro.keep_out = t->keep_out;
+  ro.out_scale = t->out_scale;
+  const PaRowOutputs* rows = t->has_rows ? &ro : nullptr;
+  hipStream_t st = as_stream(stream);
+  if (t->launch == 1)
+    return pa_prefill_internal(t->kv, t->q, t->q_stride, t->out, t->out_stride, t->row, t->p0,
+                               t->m, t->sm_scale, t->workspace, t->workspace_bytes, st, rows,
+                               t->window);
+  if (t->launch == 2)
+    return pa_prefill_packed_segs_internal(t->kv, t->q, t->q_stride, t->out, t->out_stride,
+                                           t->segs, t->nseg, t->sm_scale, t->window, t->workspace,
+                                           t->workspace_bytes, st, rows);
+  LLM_REQUIRE(t->out_kind >= 0 && t->out_kind < (int)PaOut::OPROJ,
+              "pa_rows_tune: out_kind must be F32, ROW_Q, ROW_F16 or F32_ROWS");
+  LLM_REQUIRE(t->row_group >= 1 && t->row_group <= 4, "pa_rows_tune: row_group must be in [1, 4]");
+  PaRequest rq = pa_request(t->kv, t->B, t->H, t->D, t->T, t->pages_per_split, t->row_group,
+                            (PaOut)t->out_kind, t->window);
+  rq.keep_out = t->keep_out != 0;
+  PaLaunch p;
+  const int rc = pa_decode_internal(t->kv, rq, nullptr, t->q_stride, nullptr, nullptr, nullptr,
+                                    1.f, nullptr, 0, nullptr, nullptr, &p);
+  if (rc != LLM_OK) return rc;
+  t->nsplit = p.nsplit;
+  t->form = p.form();
+  return pa_decode_internal(t->kv, rq, t->q, t->q_stride, t->out, t->beam_ids, t->context_lens,
+                            t->sm_scale, t->workspace, t->workspace_bytes, st, rows);
 }
 
 // Tuning hook (not part of include/llm_decoder.h): run the split kernel of

@@ -64,6 +64,23 @@ class WeightGemmTuneArgs(ctypes.Structure):
                 ("kv_rope", c_void_p), ("kv_rope_len", c_int)]
 
 
+class PaRowsTuneArgs(ctypes.Structure):
+    """pa_rows_tune's argument (csrc/tune/pa_decode_tune.hip, tuning library
+    only): which internal attention entry to call (launch 0 decode, 1 prefill,
+    2 packed prefill), its arguments, the PaRowOutputs fields (has_rows 0:
+    rows = NULL) and, for decode, the launch that ran (nsplit, form)."""
+    _fields_ = [("launch", c_int), ("kv", ctypes.POINTER(PaKvView)), ("q", c_void_p),
+                ("q_stride", c_int), ("sm_scale", c_float), ("window", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("beam_ids", c_void_p), ("context_lens", c_void_p), ("B", c_int), ("H", c_int),
+                ("D", c_int), ("T", c_int), ("pages_per_split", c_int), ("row_group", c_int),
+                ("out_kind", c_int), ("row", c_int), ("p0", c_int), ("m", c_int),
+                ("segs", ctypes.POINTER(PaPrefillSeg)), ("nseg", c_int), ("has_rows", c_int),
+                ("rows_q", c_void_p), ("inv_scale", c_void_p), ("out16", c_void_p),
+                ("pack", c_int), ("keep_out", c_int), ("out_scale", c_float), ("out", c_void_p),
+                ("out_stride", c_int), ("nsplit", c_int), ("form", c_int)]
+
+
 class PaDecodeOptions(ctypes.Structure):
     _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int),
                 ("top_p", ctypes.c_float), ("eos_token", ctypes.c_int),
@@ -217,6 +234,9 @@ _SIGS = {
     # tuning library only (csrc/tune/gemm_tune.hip): the decoder's weight_gemm,
     # its prologue predicates, the form launch_gemm picks and the forced forms
     "weight_gemm_tune": (c_int, [ctypes.POINTER(WeightGemmTuneArgs), c_void_p]),
+    # tuning library only (csrc/tune/pa_decode_tune.hip): the internal attention
+    # entries with their row outputs
+    "pa_rows_tune": (c_int, [ctypes.POINTER(PaRowsTuneArgs), c_void_p]),
     "gemm_ln_fusable_tune": (c_int, [c_int, c_int, c_int]),
     "gemm_quant_prologue_ok_tune": (c_int, [c_int, c_int, c_int]),
     "gemm_form_tune": (c_int, [c_int] * 9 + [c_i32p]),
@@ -522,6 +542,79 @@ def pa_prefill_packed(q, k_pool, v_pool, page_table, *, segs, sm_scale=1.0, out=
     check(lib.pa_prefill_packed(ctypes.byref(view), ptr(q), q.stride(0), ptr(out), out.stride(0),
                                 arr, len(segs), sm_scale, ptr(ws), ws_bytes, stream_ptr(stream)))
     return out
+
+
+PA_OUT_F32, PA_OUT_ROW_Q, PA_OUT_ROW_F16, PA_OUT_F32_ROWS = range(4)  # csrc/pa_plan.hpp PaOut
+PA_ROWS_SENTINEL = 0x5A  # every byte of the int8 / fp16 row buffers before the call
+
+
+def pa_rows(q, k_pool, v_pool, page_table, *, launch, out_kind, T=0, beam_ids=None,
+            context_lens=None, pages_per_split=0, row_group=1, row=0, p0=0, segs=None,
+            sm_scale=1.0, window=0, pack=1, keep_out=1, out_scale=1.0, want_out=True,
+            split=True, has_rows=True, omit=(), stream=None):
+    """pa_rows_tune (tuning library): one of the internal attention entries with
+    its row outputs, on torch device tensors.  launch "decode" (q [B][H][D]),
+    "prefill" (q [m][H][D] at positions p0 .. of page-table row `row`) or
+    "packed" (segs [(row, p0, len), ...]); out_kind PA_OUT_ROW_Q / ROW_F16 /
+    F32_ROWS says which row buffers the entry gets (the prefill entries take
+    it from the pointers alone); omit: names of buffers ("q", "inv_scale",
+    "out16") passed as NULL all the same.  want_out=False passes out = NULL;
+    split=False gives the prefill entries no split workspace (one pass).
+    Returns a dict: status, error (text of a refusal), out fp32 [rows][H*D]
+    (pre-filled with NaN) or None, q8 int8 and out16 int16 bit patterns of
+    rows16 * H*D elements when packed (rows16 = rows rounded up to 16; every
+    byte pre-filled with PA_ROWS_SENTINEL) else rows * H*D, inv_scale fp32
+    [rows] (NaN), nsplit, form (decode)."""
+    import torch
+    tune = load_tune()
+    rows = q.shape[0]
+    H, D = page_table.shape[1], k_pool.shape[2]
+    hid = H * D
+    if q.stride(-1) != 1:
+        raise ValueError("q rows must be contiguous")
+    dev = q.device
+    view = kv_view(k_pool, v_pool, page_table)
+    a = PaRowsTuneArgs()
+    a.launch = {"decode": 0, "prefill": 1, "packed": 2}[launch]
+    a.kv = ctypes.pointer(view)
+    a.q, a.q_stride, a.sm_scale, a.window = q.data_ptr(), q.stride(0), sm_scale, window
+    seg_arr = None
+    if launch == "decode":
+        ws_bytes = tune.pa_decode_workspace_bytes(rows, H, D, page_table.shape[2], pages_per_split)
+        a.beam_ids = None if beam_ids is None else beam_ids.data_ptr()
+        a.context_lens = None if context_lens is None else context_lens.data_ptr()
+        a.B, a.H, a.D, a.T = rows, H, D, T
+        a.pages_per_split, a.row_group = pages_per_split, row_group
+    elif launch == "prefill":
+        ws_bytes = tune.pa_prefill_workspace_bytes(ctypes.byref(view), p0, rows) if split else 0
+        a.row, a.p0, a.m = row, p0, rows
+    else:
+        seg_arr = prefill_segs(segs)
+        ws_bytes = tune.pa_prefill_packed_workspace_bytes(ctypes.byref(view), seg_arr, len(segs),
+                                                          1 if split else 0)
+        a.segs, a.nseg = seg_arr, len(segs)
+    a.out_kind = out_kind
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev) if ws_bytes else None
+    a.workspace, a.workspace_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws_bytes)
+    n_el = ((rows + 15) // 16 * 16 if pack else rows) * hid
+    fill16 = PA_ROWS_SENTINEL * 0x0101
+    out = torch.full((rows, hid), float("nan"), dtype=torch.float32, device=dev) if want_out else None
+    q8 = inv = out16 = None
+    if out_kind == PA_OUT_ROW_Q:
+        q8 = torch.full((n_el,), PA_ROWS_SENTINEL, dtype=torch.int8, device=dev)
+        inv = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev)
+    elif out_kind == PA_OUT_ROW_F16:
+        out16 = torch.full((n_el,), fill16, dtype=torch.int16, device=dev)
+    given = lambda name, t: None if t is None or name in omit else t.data_ptr()
+    a.has_rows = 1 if has_rows else 0
+    a.rows_q, a.inv_scale, a.out16 = given("q", q8), given("inv_scale", inv), given("out16", out16)
+    a.pack, a.keep_out, a.out_scale = pack, keep_out, out_scale
+    a.out = None if out is None else out.data_ptr()
+    status = tune.pa_rows_tune(ctypes.byref(a), stream_ptr(stream))
+    torch.cuda.synchronize()
+    msg = tune.llm_last_error() if status != LLM_OK else b""
+    return dict(status=status, error=(msg or b"").decode(), out=out, q8=q8, inv_scale=inv,
+                out16=out16, nsplit=a.nsplit, form=a.form)
 
 
 def pack_weights(W, dtype: int, stream=None):
