@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "decoder_impl.hpp"
+#include "oproj_slices.hpp"
 
 // ---------------------------------------------------------------------------
 // weights
@@ -111,17 +112,11 @@ extern "C" int llm_decoder_set_f16_weights(llm_decoder* d, const llm_f16_weights
   // the bytes a step streams (w_keep_for) are unchanged
   d->wo_heads.alloc(0);
   if (d->D % 8 == 0 && d->D <= 128 && d->H <= 64 && oproj_fuse_on()) {
-    const int D = d->D, KG = D / 8;
     const uint16_t* src = static_cast<const uint16_t*>(w->wo);
     std::vector<uint16_t> sl((size_t)hid * hid);
     RET_IF(d->wo_heads.alloc((size_t)L * hid * hid));
     for (int l = 0; l < L; ++l) {
-      const uint16_t* wl = src + (size_t)l * hid * hid;
-      for (int h = 0; h < d->H; ++h)
-        for (int kg = 0; kg < KG; ++kg)
-          for (int n = 0; n < hid; ++n)
-            for (int j = 0; j < 8; ++j)
-              sl[(((size_t)h * KG + kg) * hid + n) * 8 + j] = wl[(size_t)(h * D + 8 * kg + j) * hid + n];
+      oproj_head_slices(src + (size_t)l * hid * hid, d->H, d->D, hid, sl.data());
       LLM_HIP_RET(hipMemcpy(d->wo_heads.p + (size_t)l * hid * hid, sl.data(),
                             sizeof(uint16_t) * hid * hid, hipMemcpyHostToDevice));
     }

@@ -9,13 +9,14 @@
 // PaSplitCfg fields it changes), pa_plan_tune, the planner's test entry,
 // prefill_passes_tune, the prefill pass packer's, serve_plan_sim_tune, the
 // continuous-batching scheduler's, beam_book_tune, the beam search
-// bookkeeping's, and pa_rows_tune, the internal attention entries with their
-// row outputs.
+// bookkeeping's, oproj_head_slices_tune, the fused o_proj's W_o layout, and
+// pa_rows_tune, the internal attention entries with their row outputs.
 #include <cmath>
 
 #include "tune/pa_decode_tune.hpp"
 #include "tune/pa_beam_steal.hpp"
 #include "beam_plan.hpp"
+#include "oproj_slices.hpp"
 #include "pa_tuning.hpp"
 #include "prefill_pack.hpp"
 #include "serve_plan.hpp"
@@ -1177,6 +1178,17 @@ extern "C" int beam_book_tune(const float* cand_score, const int32_t* cand_paren
   return LLM_OK;
 }
 
+// Tuning hook: the fused o_proj's W_o head slices (oproj_slices.hpp) of one
+// row-major fp16 [H*D][o_n] matrix, on the host, as llm_decoder_set_f16_weights
+// builds them per layer: out [H][D/8][o_n][8].
+extern "C" int oproj_head_slices_tune(const uint16_t* wo, int H, int D, int o_n, uint16_t* out) {
+  LLM_REQUIRE(wo && out, "oproj_head_slices_tune: NULL");
+  LLM_REQUIRE(H >= 1 && D >= 8 && D % 8 == 0 && o_n >= 1,
+              "oproj_head_slices_tune: H, o_n >= 1, D a positive multiple of 8");
+  oproj_head_slices(wo, H, D, o_n, out);
+  return LLM_OK;
+}
+
 // Tuning hook: the three internal attention entries (pa_decode_internal,
 // pa_prefill_internal, pa_prefill_packed_segs_internal) unchanged behind a
 // plain-C struct, so tests reach what the decoder's layers get back -- the
@@ -1196,7 +1208,7 @@ struct PaRowsTuneArgs {
   const int32_t* beam_ids;
   const int32_t* context_lens;
   int B, H, D, T, pages_per_split, row_group;
-  int out_kind;  // PaOut: 1 ROW_Q, 2 ROW_F16, 3 F32_ROWS (0 F32; OPROJ is not reached here)
+  int out_kind;  // PaOut: 0 F32, 1 ROW_Q, 2 ROW_F16, 3 F32_ROWS, 4 OPROJ
   // prefill: positions p0 .. p0 + m - 1 of page-table row `row`
   int row, p0, m;
   // packed prefill: the segment list (host); the workspace starts with
@@ -1214,6 +1226,13 @@ struct PaRowsTuneArgs {
   int out_stride;  // prefill entries (0: H*D)
   // decode: the launch that ran (written before it runs; 0 / 0 if refused before the plan)
   int nsplit, form;
+  // decode, out_kind OPROJ: PaRowOutputs' fused o_proj fields and PaRequest::rows16
+  long long* o_acc;
+  float* o_x;
+  const void* wo_heads;
+  int o_n;
+  int* o_flag;
+  int rows16;
 };
 
 extern "C" int pa_rows_tune(PaRowsTuneArgs* t, void* stream) {
@@ -1237,12 +1256,17 @@ extern "C" int pa_rows_tune(PaRowsTuneArgs* t, void* stream) {
     return pa_prefill_packed_segs_internal(t->kv, t->q, t->q_stride, t->out, t->out_stride,
                                            t->segs, t->nseg, t->sm_scale, t->window, t->workspace,
                                            t->workspace_bytes, st, rows);
-  LLM_REQUIRE(t->out_kind >= 0 && t->out_kind < (int)PaOut::OPROJ,
-              "pa_rows_tune: out_kind must be F32, ROW_Q, ROW_F16 or F32_ROWS");
+  LLM_REQUIRE(t->out_kind >= 0 && t->out_kind <= (int)PaOut::OPROJ,
+              "pa_rows_tune: out_kind must be F32, ROW_Q, ROW_F16, F32_ROWS or OPROJ");
   LLM_REQUIRE(t->row_group >= 1 && t->row_group <= 4, "pa_rows_tune: row_group must be in [1, 4]");
   PaRequest rq = pa_request(t->kv, t->B, t->H, t->D, t->T, t->pages_per_split, t->row_group,
                             (PaOut)t->out_kind, t->window);
   rq.keep_out = t->keep_out != 0;
+  if (rq.out == PaOut::OPROJ) {
+    rq.rows16 = t->rows16 != 0;
+    ro.o_acc = t->o_acc, ro.o_x = t->o_x, ro.wo_heads = t->wo_heads, ro.o_n = t->o_n;
+    ro.o_flag = t->o_flag;
+  }
   PaLaunch p;
   const int rc = pa_decode_internal(t->kv, rq, nullptr, t->q_stride, nullptr, nullptr, nullptr,
                                     1.f, nullptr, 0, nullptr, nullptr, &p);

@@ -68,7 +68,8 @@ class PaRowsTuneArgs(ctypes.Structure):
     """pa_rows_tune's argument (csrc/tune/pa_decode_tune.hip, tuning library
     only): which internal attention entry to call (launch 0 decode, 1 prefill,
     2 packed prefill), its arguments, the PaRowOutputs fields (has_rows 0:
-    rows = NULL) and, for decode, the launch that ran (nsplit, form)."""
+    rows = NULL), for decode the launch that ran (nsplit, form), and the fused
+    o_proj's fields (out_kind PA_OUT_OPROJ)."""
     _fields_ = [("launch", c_int), ("kv", ctypes.POINTER(PaKvView)), ("q", c_void_p),
                 ("q_stride", c_int), ("sm_scale", c_float), ("window", c_int),
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t),
@@ -78,7 +79,9 @@ class PaRowsTuneArgs(ctypes.Structure):
                 ("segs", ctypes.POINTER(PaPrefillSeg)), ("nseg", c_int), ("has_rows", c_int),
                 ("rows_q", c_void_p), ("inv_scale", c_void_p), ("out16", c_void_p),
                 ("pack", c_int), ("keep_out", c_int), ("out_scale", c_float), ("out", c_void_p),
-                ("out_stride", c_int), ("nsplit", c_int), ("form", c_int)]
+                ("out_stride", c_int), ("nsplit", c_int), ("form", c_int),
+                ("o_acc", c_void_p), ("o_x", c_void_p), ("wo_heads", c_void_p), ("o_n", c_int),
+                ("o_flag", c_void_p), ("rows16", c_int)]
 
 
 class PaDecodeOptions(ctypes.Structure):
@@ -237,6 +240,8 @@ _SIGS = {
     # tuning library only (csrc/tune/pa_decode_tune.hip): the internal attention
     # entries with their row outputs
     "pa_rows_tune": (c_int, [ctypes.POINTER(PaRowsTuneArgs), c_void_p]),
+    # tuning library only: the fused o_proj's W_o head slices (csrc/oproj_slices.hpp), host only
+    "oproj_head_slices_tune": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "gemm_ln_fusable_tune": (c_int, [c_int, c_int, c_int]),
     "gemm_quant_prologue_ok_tune": (c_int, [c_int, c_int, c_int]),
     "gemm_form_tune": (c_int, [c_int] * 9 + [c_i32p]),
@@ -544,14 +549,29 @@ def pa_prefill_packed(q, k_pool, v_pool, page_table, *, segs, sm_scale=1.0, out=
     return out
 
 
-PA_OUT_F32, PA_OUT_ROW_Q, PA_OUT_ROW_F16, PA_OUT_F32_ROWS = range(4)  # csrc/pa_plan.hpp PaOut
-PA_ROWS_SENTINEL = 0x5A  # every byte of the int8 / fp16 row buffers before the call
+# csrc/pa_plan.hpp PaOut
+PA_OUT_F32, PA_OUT_ROW_Q, PA_OUT_ROW_F16, PA_OUT_F32_ROWS, PA_OUT_OPROJ = range(5)
+PA_ROWS_SENTINEL = 0x5A  # every byte of the int8 / fp16 row buffers (and of o_x) before the call
+
+
+def oproj_head_slices(wo, H, D):
+    """oproj_head_slices_tune (tuning library, host only): a host fp16 W_o
+    [H*D][o_n] as the fused o_proj's head slices, uint16 [H][D/8][o_n][8]."""
+    import numpy as np
+    wo = np.ascontiguousarray(wo, dtype=np.float16)
+    if wo.ndim != 2 or wo.shape[0] != H * D:
+        raise ValueError("W_o must be [H*D][o_n]")
+    tune = load_tune()
+    out = np.empty((H, D // 8, wo.shape[1], 8), np.uint16)
+    check(tune.oproj_head_slices_tune(wo.ctypes.data, H, D, wo.shape[1], out.ctypes.data), tune)
+    return out
 
 
 def pa_rows(q, k_pool, v_pool, page_table, *, launch, out_kind, T=0, beam_ids=None,
             context_lens=None, pages_per_split=0, row_group=1, row=0, p0=0, segs=None,
             sm_scale=1.0, window=0, pack=1, keep_out=1, out_scale=1.0, want_out=True,
-            split=True, has_rows=True, omit=(), stream=None):
+            split=True, has_rows=True, omit=(), stream=None, wo=None, o_n=None, o_acc=None,
+            o_flag=None, rows16=0, sync=True):
     """pa_rows_tune (tuning library): one of the internal attention entries with
     its row outputs, on torch device tensors.  launch "decode" (q [B][H][D]),
     "prefill" (q [m][H][D] at positions p0 .. of page-table row `row`) or
@@ -564,7 +584,16 @@ def pa_rows(q, k_pool, v_pool, page_table, *, launch, out_kind, T=0, beam_ids=No
     (pre-filled with NaN) or None, q8 int8 and out16 int16 bit patterns of
     rows16 * H*D elements when packed (rows16 = rows rounded up to 16; every
     byte pre-filled with PA_ROWS_SENTINEL) else rows * H*D, inv_scale fp32
-    [rows] (NaN), nsplit, form (decode)."""
+    [rows] (NaN), nsplit, form (decode).
+    out_kind PA_OUT_OPROJ (decode; the FP16 decoder's fused o_proj): wo is the
+    host fp16 W_o [H*D][o_n], sliced by oproj_head_slices and uploaded; o_n
+    overrides the column count the launch is told; o_acc int64 [(rows + 1) *
+    o_n] and o_flag int32 [1] are the caller's buffers of an earlier launch, or
+    allocated as zeros; rows16 asks for out16 as well; omit may name "o_flag".
+    The dict then also holds x fp32 [rows + 1][o_n] (every byte pre-filled
+    with PA_ROWS_SENTINEL; the last row is never the launch's), o_acc as the
+    launch left it and o_flag.  sync=False returns without waiting for the
+    launch (launches back to back on one stream)."""
     import torch
     tune = load_tune()
     rows = q.shape[0]
@@ -603,18 +632,34 @@ def pa_rows(q, k_pool, v_pool, page_table, *, launch, out_kind, T=0, beam_ids=No
     if out_kind == PA_OUT_ROW_Q:
         q8 = torch.full((n_el,), PA_ROWS_SENTINEL, dtype=torch.int8, device=dev)
         inv = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev)
-    elif out_kind == PA_OUT_ROW_F16:
+    elif out_kind == PA_OUT_ROW_F16 or (out_kind == PA_OUT_OPROJ and rows16):
         out16 = torch.full((n_el,), fill16, dtype=torch.int16, device=dev)
     given = lambda name, t: None if t is None or name in omit else t.data_ptr()
+    x = heads = None
+    if out_kind == PA_OUT_OPROJ:
+        heads = torch.from_numpy(oproj_head_slices(wo, H, D).view("int16")).to(dev)
+        cols = heads.shape[2]
+        x = torch.full(((rows + 1) * cols * 4,), PA_ROWS_SENTINEL, dtype=torch.uint8,
+                       device=dev).view(torch.float32).view(rows + 1, cols)
+        if o_acc is None:
+            o_acc = torch.zeros(((rows + 1) * cols,), dtype=torch.int64, device=dev)
+        if o_flag is None:
+            o_flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+        a.o_acc, a.o_x, a.wo_heads = o_acc.data_ptr(), x.data_ptr(), heads.data_ptr()
+        a.o_n, a.o_flag, a.rows16 = cols if o_n is None else o_n, given("o_flag", o_flag), rows16
     a.has_rows = 1 if has_rows else 0
     a.rows_q, a.inv_scale, a.out16 = given("q", q8), given("inv_scale", inv), given("out16", out16)
     a.pack, a.keep_out, a.out_scale = pack, keep_out, out_scale
     a.out = None if out is None else out.data_ptr()
     status = tune.pa_rows_tune(ctypes.byref(a), stream_ptr(stream))
-    torch.cuda.synchronize()
+    if sync:
+        torch.cuda.synchronize()
     msg = tune.llm_last_error() if status != LLM_OK else b""
-    return dict(status=status, error=(msg or b"").decode(), out=out, q8=q8, inv_scale=inv,
-                out16=out16, nsplit=a.nsplit, form=a.form)
+    res = dict(status=status, error=(msg or b"").decode(), out=out, q8=q8, inv_scale=inv,
+               out16=out16, nsplit=a.nsplit, form=a.form)
+    if out_kind == PA_OUT_OPROJ:
+        res.update(x=x, o_acc=o_acc, o_flag=o_flag, wo_heads=heads)  # (wo_heads: kept alive)
+    return res
 
 
 def pack_weights(W, dtype: int, stream=None):
