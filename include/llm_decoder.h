@@ -387,6 +387,39 @@ int sample_rows_each(const float* logits, int rows, int V, const float* temperat
  * at the largest num_seqs first); calls on different streams must not overlap. */
 int beam_select_rows(const float* logits, const float* score_in, int num_seqs, int W, int V,
                      float* cand_score, int32_t* cand_parent, int32_t* cand_token, void* stream);
+/* Log-probabilities.  For a logits row x of V entries, m = max x and
+ * s = sum_v exp(x_v - m) in fp32:
+ *   lse = log(s + 1e-6),   logprob(t) = (x_t - m) - lse
+ * -- beam_select_rows' term, so a hypothesis's sum_logprob and the score of
+ * the same ids mean the same thing.  Always of the raw logits: temperature 1,
+ * before top-k / top-p.
+ *
+ * lm_head_logprobs: the LM head with a log-softmax epilogue (csrc/lm_head.hip).
+ * x, E, M, V, K as lm_head (E is packed once per call); targets int32 [M]
+ * device.  logprob[r] = logprob(targets[r]) of row r's logits; a target outside
+ * [0, V) is an ignore index: logprob[r] = 0 and a target logit of 0.  stats
+ * (may be NULL) fp32 [M][3] = {m, lse, x_target}.  No [M][V] logits are written
+ * anywhere: the MFMA sequence is lm_head's (the same logits in registers, bit
+ * for bit), reduced per (row, workgroup) to {max, sum exp(x - max), target
+ * logit}, and a merge launch combines the partials per row in a fixed order.
+ * Two launches, no atomics, the same bits on every run.  LLM_ERR_INVALID, on
+ * the host before any launch, for a NULL operand (stats excepted),
+ * K % 32 != 0, or a packed E past 32-bit offsets; M == 0 is a no-op. */
+int lm_head_logprobs(const float* x, const void* E, const int32_t* targets, float* logprob,
+                     float* stats, int M, int V, int K, void* stream);
+/* logprob_rows: chosen and top-n log-probabilities of materialised rows
+ * (csrc/logprobs.hip; one workgroup per row, one launch).  logits fp32
+ * [rows][V] device.  chosen (int32 [rows] device, may be NULL): chosen_lp[r] =
+ * logprob(chosen[r]); an id outside [0, V) is an ignore index and writes 0.
+ * top_n in 0 .. LLM_MAX_TOP_LOGPROBS: top_id[r][j] / top_lp[r][j], j < top_n
+ * (stride top_n), are the row's top_n largest RAW logits ordered by (logit
+ * descending, token id ascending) with their log-probabilities.  stats (may be
+ * NULL) fp32 [rows][2] = {m, lse}.  LLM_ERR_INVALID on the host for top_n
+ * outside 0..8, V < max(1, top_n), V > 65536, or a NULL output that the
+ * arguments require (chosen_lp with chosen; top_lp / top_id with top_n > 0). */
+#define LLM_MAX_TOP_LOGPROBS 8
+int logprob_rows(const float* logits, int rows, int V, const int32_t* chosen, int top_n,
+                 float* chosen_lp, float* top_lp, int32_t* top_id, float* stats, void* stream);
 /* The uniform draw sample_rows uses for (seed, row, counter): splitmix64 of
  * seed ^ (row << 32) ^ counter, top 24 bits / 2^24. */
 float sample_uniform_host(uint64_t seed, int row, int counter);
@@ -737,6 +770,27 @@ int llm_decoder_prefill_rows(llm_decoder* d, const int32_t* rows, const int32_t*
 int llm_decoder_set_packed_prefill(llm_decoder* d, int on);
 int llm_decoder_packed_prefill(const llm_decoder* d);
 
+/* Teacher-forced scoring through the prefill passes: tokens host
+ * [nseq][stride], lens[s] >= 1 ids each; out_logprob host [nseq][stride]:
+ *   out[s][i] = log p(tokens[s][i] | tokens[s][0 .. i-1])   for 1 <= i < lens[s]
+ * (logprob() of lm_head_logprobs), out[s][0] = 0, entries from lens[s] on are
+ * untouched.  Sequences are taken in order in groups of at most max_batch rows
+ * whose page needs -- per sequence the pages of lens[s] - 1 positions, by the
+ * rule a served request is charged (window-aware) -- fit the pool together.
+ * Each group's tokens[:len-1] go through llm_decoder_prefill_rows' packed
+ * passes if packed prefill is on, else row by row; after the layers of each
+ * pass ONE lm_head_logprobs launch pair runs over all packed rows against
+ * their next tokens, and only one value per row is copied back: no logits are
+ * materialised and the pass's own token choice is skipped.  lens[s] == 1
+ * produces nothing.  LLM_ERR_INVALID with nothing run: lens[s] < 1 or > stride,
+ * an id out of range, lens[s] - 1 >= max_seq_len, a sequence whose need
+ * exceeds the pool, or while serving.  Works with both weight types, fp16 /
+ * LLM_FP8 pages, rope, a window and packed prefill.  On return no rows are
+ * active and the cache is clear, as after llm_decoder_serve_end.  (Prefill
+ * passes never run the fused o_proj, so LLM_ERR_RANGE does not arise here.) */
+int llm_decoder_score(llm_decoder* d, const int32_t* tokens, const int32_t* lens, int stride,
+                      int nseq, float* out_logprob);
+
 /* Token choice of every following step: greedy argmax (temperature <= 0 or
  * top_k == 1; the default, sample_from_logits, decoder/cuda_decoder.cu:7-14)
  * or device sampling with temperature / top_k / top_p (sample_rows; the draw
@@ -805,6 +859,27 @@ int llm_decoder_serve_end(llm_decoder* d);
  * T > max_seq_len, or a need above the pool's num_pages. */
 int llm_decoder_submit(llm_decoder* d, const int32_t* prompt, int n,
                        const llm_request_options* opt, long long* id);
+/* llm_decoder_submit for a request that wants log-probabilities: top_logprobs
+ * 0 asks for the chosen token's only, 1 .. LLM_MAX_TOP_LOGPROBS for that many
+ * top alternatives beside it; < 0 or > 8 is LLM_ERR_INVALID.  (llm_decoder_submit
+ * asks for nothing.)  A step whose live rows include at least one asking request
+ * carries one more launch after sample_rows_each: logprob_rows over ALL live
+ * rows with chosen = the step's ids and top_n = 8 -- constants that do not
+ * depend on the request mix -- and device-to-host copies that complete with
+ * the step's own synchronisation.  Whether the launch is in the step graph is
+ * part of the graph's identity: a change re-instantiates it and counts in
+ * graph_instantiations.  A run in which nobody asks executes exactly the graph
+ * of llm_decoder_submit-only serving. */
+int llm_decoder_submit_logprobs(llm_decoder* d, const int32_t* prompt, int n,
+                                const llm_request_options* opt, int top_logprobs, long long* id);
+/* The last llm_decoder_serve_step's log-probabilities, in event (row) order:
+ * host arrays chosen_lp [max_batch], top_lp / top_id [max_batch][8], top_n
+ * [max_batch].  top_n[r] is event r's request's count (its first top_n[r]
+ * entries of row r are valid, ordered as logprob_rows orders them), or -1 for a
+ * request that did not ask: its entries are then unspecified.  Any array may
+ * be NULL.  LLM_ERR_INVALID if not serving. */
+int llm_decoder_serve_logprobs(llm_decoder* d, float* chosen_lp, float* top_lp, int32_t* top_id,
+                               int32_t* top_n);
 /* Drop a request: a waiting one leaves the queue, a live one is retired at
  * once by the row move of a retirement (nothing is in flight between steps)
  * and its pages return.  No event is emitted.  Unknown or finished id:

@@ -311,12 +311,63 @@ class Decoder {
     py::gil_scoped_release nogil;
     check(llm_decoder_serve_end(d_));
   }
+  // logprobs: None (nothing asked), or 0 .. 8: the chosen token's
+  // log-probability plus that many top alternatives (serve_logprobs)
   long long submit(const std::vector<int32_t>& tokens, int max_new_tokens, int eos_token_id,
-                   float temperature, int top_k, float top_p, uint64_t seed) {
+                   float temperature, int top_k, float top_p, uint64_t seed, py::object logprobs) {
     llm_request_options o{max_new_tokens, eos_token_id, temperature, top_k, top_p, seed};
     long long id = -1;
-    check(llm_decoder_submit(d_, tokens.data(), (int)tokens.size(), &o, &id));
+    if (logprobs.is_none()) check(llm_decoder_submit(d_, tokens.data(), (int)tokens.size(), &o, &id));
+    else
+      check(llm_decoder_submit_logprobs(d_, tokens.data(), (int)tokens.size(), &o,
+                                        logprobs.cast<int>(), &id));
     return id;
+  }
+  // The last serve_step's log-probabilities, one entry per event in event order:
+  // (logprob of the chosen token, [(id, logprob), ...] of the request's top
+  // alternatives), or None for a request that did not ask.
+  py::list serve_logprobs() {
+    const size_t B = (size_t)std::max(cfg_.max_batch, 1);
+    std::vector<float> clp(B), tlp(B * LLM_MAX_TOP_LOGPROBS);
+    std::vector<int32_t> tid(B * LLM_MAX_TOP_LOGPROBS), tn(B, -2);
+    check(llm_decoder_serve_logprobs(d_, clp.data(), tlp.data(), tid.data(), tn.data()));
+    py::list res;
+    for (size_t r = 0; r < B && tn[r] != -2; ++r) res.append(logprob_entry(clp, tlp, tid, tn, r));
+    return res;
+  }
+  static py::object logprob_entry(const std::vector<float>& clp, const std::vector<float>& tlp,
+                                  const std::vector<int32_t>& tid, const std::vector<int32_t>& tn,
+                                  size_t r) {
+    if (tn[r] < 0) return py::none();
+    py::list top;
+    for (int j = 0; j < tn[r]; ++j)
+      top.append(py::make_tuple(tid[r * LLM_MAX_TOP_LOGPROBS + j], tlp[r * LLM_MAX_TOP_LOGPROBS + j]));
+    return py::make_tuple(clp[r], top);
+  }
+  // Teacher-forced scoring (llm_decoder_score): per sequence a float32 array of
+  // len - 1 values, entry i - 1 = log p(seq[i] | seq[:i]).
+  py::list score(const std::vector<std::vector<int32_t>>& sequences) {
+    const int n = (int)sequences.size();
+    size_t stride = 1;
+    for (const auto& q : sequences) stride = std::max(stride, q.size());
+    std::vector<int32_t> toks((size_t)n * stride, 0), lens(n);
+    for (int s = 0; s < n; ++s) {
+      lens[s] = (int)sequences[s].size();
+      std::copy(sequences[s].begin(), sequences[s].end(), toks.begin() + (size_t)s * stride);
+    }
+    std::vector<float> out((size_t)n * stride, 0.f);
+    {
+      py::gil_scoped_release nogil;
+      check(llm_decoder_score(d_, toks.data(), lens.data(), (int)stride, n, out.data()));
+    }
+    py::list res;
+    for (int s = 0; s < n; ++s) {
+      py::array_t<float> a((py::ssize_t)(lens[s] - 1));
+      std::copy(out.begin() + (size_t)s * stride + 1, out.begin() + (size_t)s * stride + lens[s],
+                a.mutable_data());
+      res.append(a);
+    }
+    return res;
   }
   void cancel(long long id) { check(llm_decoder_cancel(d_, id)); }
   // [(id, token, index, row, finish), ...] of the step's live rows, ascending
@@ -347,10 +398,18 @@ class Decoder {
   // Any number of prompts through the serve loop: the generated ids per prompt
   // in submission order (EOS included where hit).  max_new_tokens: one int or
   // one per prompt; prompt i draws with seed + i.
-  std::vector<std::vector<int>> generate_many(const std::vector<std::vector<int32_t>>& prompts,
-                                              py::object max_new_tokens, int eos_token_id,
-                                              float temperature, int top_k, float top_p,
-                                              uint64_t seed) {
+  // logprobs (None, or 0 .. 8): with it the result is (ids, logprobs), logprobs
+  // per prompt one serve_logprobs entry per generated token.
+  py::object generate_many(const std::vector<std::vector<int32_t>>& prompts,
+                           py::object max_new_tokens, int eos_token_id, float temperature,
+                           int top_k, float top_p, uint64_t seed, py::object logprobs) {
+    const bool want_lp = !logprobs.is_none();
+    const int top_lp = want_lp ? logprobs.cast<int>() : -1;
+    const size_t B = (size_t)std::max(cfg_.max_batch, 1);
+    struct TokenLp { float lp; std::vector<std::pair<int32_t, float>> top; };
+    std::vector<std::vector<TokenLp>> lps(prompts.size());
+    std::vector<float> clp(B), tlp(B * LLM_MAX_TOP_LOGPROBS);
+    std::vector<int32_t> tid(B * LLM_MAX_TOP_LOGPROBS), tn(B);
     const size_t n = prompts.size();
     std::vector<int> max_new;
     if (py::isinstance<py::int_>(max_new_tokens)) max_new.assign(n, max_new_tokens.cast<int>());
@@ -358,15 +417,32 @@ class Decoder {
     if (max_new.size() != n)
       throw std::invalid_argument("generate_many: max_new_tokens must be an int or one per prompt");
     std::vector<std::vector<int>> out(n);
-    if (n == 0) return out;
+    auto result = [&]() -> py::object {
+      if (!want_lp) return py::cast(out);
+      py::list all;
+      for (const auto& per : lps) {
+        py::list one;
+        for (const TokenLp& t : per) {
+          py::list top;
+          for (const auto& p : t.top) top.append(py::make_tuple(p.first, p.second));
+          one.append(py::make_tuple(t.lp, top));
+        }
+        all.append(one);
+      }
+      return py::make_tuple(py::cast(out), all);
+    };
+    if (n == 0) return result();
     std::vector<llm_serve_event> ev((size_t)std::max(cfg_.max_batch, 1));
+    {
     py::gil_scoped_release nogil;
     check(llm_decoder_serve_begin(d_));
     int rc = LLM_OK, range_rc = LLM_OK;
     for (size_t i = 0; i < n && rc == LLM_OK; ++i) {
       llm_request_options o{max_new[i], eos_token_id, temperature, top_k, top_p, seed + i};
       long long id = -1;
-      rc = llm_decoder_submit(d_, prompts[i].data(), (int)prompts[i].size(), &o, &id);
+      rc = want_lp ? llm_decoder_submit_logprobs(d_, prompts[i].data(), (int)prompts[i].size(), &o,
+                                                 top_lp, &id)
+                   : llm_decoder_submit(d_, prompts[i].data(), (int)prompts[i].size(), &o, &id);
     }
     for (size_t left = n; rc == LLM_OK && left > 0;) {
       int ne = 0;
@@ -377,9 +453,18 @@ class Decoder {
         throw std::runtime_error("llm_decoder: generate_many: a serve step returned no event "
                                  "with requests outstanding");
       }
-      for (int j = 0; j < ne; ++j) {
+      if (rc == LLM_OK && want_lp && ne > 0)
+        rc = llm_decoder_serve_logprobs(d_, clp.data(), tlp.data(), tid.data(), tn.data());
+      for (int j = 0; rc == LLM_OK && j < ne; ++j) {
         out[(size_t)ev[j].id].push_back(ev[j].token);
         left -= ev[j].finish != 0;
+        if (want_lp) {
+          TokenLp t{clp[j], {}};
+          for (int k = 0; k < tn[j]; ++k)
+            t.top.emplace_back(tid[(size_t)j * LLM_MAX_TOP_LOGPROBS + k],
+                               tlp[(size_t)j * LLM_MAX_TOP_LOGPROBS + k]);
+          lps[(size_t)ev[j].id].push_back(std::move(t));
+        }
       }
     }
     std::string err = rc != LLM_OK ? llm_last_error() : "";
@@ -389,7 +474,8 @@ class Decoder {
     if (range_rc)
       throw std::runtime_error("llm_decoder: generate_many: the fused o_proj clamped a head "
                                "product in at least one step");
-    return out;
+    }
+    return result();
   }
 
   void begin_beams(int num_seqs, int beam_width, int shared_len, int beam_len, uint64_t seed,
@@ -732,7 +818,9 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("serve_begin", &Decoder::serve_begin)
         .def("submit", &Decoder::submit, py::arg("tokens"), py::arg("max_new_tokens"),
              py::arg("eos_token_id") = -1, py::arg("temperature") = 0.0f, py::arg("top_k") = 0,
-             py::arg("top_p") = 1.0f, py::arg("seed") = 0)
+             py::arg("top_p") = 1.0f, py::arg("seed") = 0, py::arg("logprobs") = py::none())
+        .def("serve_logprobs", &Decoder::serve_logprobs)
+        .def("score", &Decoder::score, py::arg("sequences"))
         .def("cancel", &Decoder::cancel, py::arg("id"))
         .def("serve_step", &Decoder::serve_step, py::arg("logits_ptr") = 0)
         .def("serve_stats", &Decoder::serve_stats)
@@ -740,7 +828,7 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("generate_many", &Decoder::generate_many, py::arg("prompts"),
              py::arg("max_new_tokens"), py::arg("eos_token_id") = -1,
              py::arg("temperature") = 0.0f, py::arg("top_k") = 0, py::arg("top_p") = 1.0f,
-             py::arg("seed") = 0)
+             py::arg("seed") = 0, py::arg("logprobs") = py::none())
         .def("begin_beams", &Decoder::begin_beams, py::arg("num_seqs"), py::arg("beam_width"),
              py::arg("shared_len"), py::arg("beam_len"), py::arg("seed") = 0,
              py::arg("shuffle") = true)

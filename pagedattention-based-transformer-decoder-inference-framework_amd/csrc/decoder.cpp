@@ -29,6 +29,7 @@
 //                        fused o_proj's range report
 //   decoder_prefill.cpp  chunked and packed prefill
 //   decoder_serve.cpp    continuous batching (serve_plan.hpp's decisions)
+//   decoder_score.cpp    teacher-forced scoring through the prefill passes
 //   decoder_beam.cpp     beam search (beam_plan.hpp's bookkeeping)
 //   decoder_weights.cpp  weight upload, the weight-file reader, the quantiser
 #include <algorithm>
@@ -126,6 +127,7 @@ static int create_decoder(const llm_decoder_config* cfg_in, int kv_dtype, llm_de
   // C4 -5 %, C3 -0.5..+1 %: the branches do not overlap usefully, and a
   // saturating KV scan slows the other half's glue 4-8x).
   d->use_graph = env_int("LLM_GRAPH", 1) != 0;
+  d->score_form = env_int("LLM_SCORE_FORM", 0);  // (decoder_impl.hpp; 0: the fused launch pair)
   d->h_pos.assign(B, 0);
   *out = d.release();
   return LLM_OK;

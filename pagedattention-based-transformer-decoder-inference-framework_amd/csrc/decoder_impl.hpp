@@ -224,7 +224,8 @@ struct llm_decoder {
   DevBuf<float> px, pq, po, ph1, psa;
   DevBuf<uint8_t> pact, pws;
   DevBuf<int32_t> pmeta;  // [4][chunk]: pos, ctx, page-table row, token; then the
-                          // packed passes' tile table [<= chunk][4]
+                          // packed passes' tile table [<= chunk][4]; then a
+                          // scoring pass's targets [chunk]
   size_t pws_bytes = 0;
   int pf_cap = 0;
   int prefill_reserve(int C);
@@ -241,6 +242,26 @@ struct llm_decoder {
   int prefill_prompts(const int32_t* prompts, const int32_t* prompt_lens, int prompt_stride, int n,
                       int row_step);
 
+  // Scoring (llm_decoder_score, decoder_score.cpp).  While `scoring` is set a
+  // prefill pass ends with ONE launch_lm_head_logprobs over its packed rows
+  // instead of a token choice: the targets (each packed row's next token of its
+  // own sequence, seq[row]) are uploaded behind the pass's meta, and the m
+  // values are copied back into out[row] at the target's position.
+  struct ScoreRows {
+    std::vector<const int32_t*> seq;  // per active row: its whole sequence
+    std::vector<float*> out;          // per active row: its out_logprob row
+  };
+  const ScoreRows* scoring = nullptr;
+  DevBuf<float> lp_ws, lp_val;  // the launch pair's partials; [kPrefillChunk] results
+  // LLM_SCORE_FORM (read at create, scripts/bench_score.py's arms): 0 the fused
+  // launch pair; 1 the unfused alternative (launch_lm_head writing the pass's
+  // logits into lp_logits, then launch_logprob_rows with chosen = the targets);
+  // 2 no LM head at all (the floor: the values are not computed)
+  int score_form = 0;
+  DevBuf<float> lp_logits;  // form 1 only: [kPrefillChunk][V]
+  std::vector<float> h_lp;
+  int score(const int32_t* toks, const int32_t* lens, int stride, int nseq, float* out);
+
   // Continuous batching (llm_decoder_serve_*).  `plan` (serve_plan.hpp) owns
   // the policy -- who is admitted, which row a request holds, which row moves
   // at a retirement -- and the functions below execute its decisions: the
@@ -252,7 +273,20 @@ struct llm_decoder {
     std::vector<int32_t> prompt;
     llm_request_options opt;
     int32_t feed;  // the token its next step takes: prompt's last, then the chosen id
+    int top_logprobs = -1;  // llm_decoder_submit_logprobs' count; -1: did not ask
   };
+  // Log-probabilities while serving: step_logprobs (a live request asks) puts
+  // one launch_logprob_rows over all live rows (chosen = the step's ids, top_n
+  // = LLM_MAX_TOP_LOGPROBS) behind the token choice; it is part of the step
+  // graph's identity (serve_step drops the graph when it changes).  run_step
+  // copies sl_* to hl_* before its closing synchronisation; hl_topn holds the
+  // last step's events' counts (hl_n of them).
+  bool step_logprobs = false;
+  DevBuf<float> sl_chosen, sl_top_lp;
+  DevBuf<int32_t> sl_top_id;
+  std::vector<float> hl_chosen, hl_top_lp;
+  std::vector<int32_t> hl_top_id, hl_topn;
+  int hl_n = 0;
   bool serving = false;
   ServePlan plan;
   std::unordered_map<long long, ServeRequest> requests;  // waiting and live, by id

@@ -19,7 +19,7 @@ int llm_decoder::prefill_reserve(int C) {
     RET_IF(ph1.alloc((size_t)C * inter));
     RET_IF(psa.alloc((size_t)C));
     RET_IF(pact.alloc(C16 * std::max(hid, inter) * (wdtype == LLM_I8 ? 1 : 4)));  // F16: act, act2
-    RET_IF(pmeta.alloc((size_t)8 * C));
+    RET_IF(pmeta.alloc((size_t)9 * C));
     pws_bytes = 16;
     for (int b = 1; b <= C; ++b)
       pws_bytes = std::max(pws_bytes, pa_decode_workspace_bytes(b, H, D, max_tiles, 0));
@@ -94,6 +94,13 @@ int llm_decoder::prefill_pass(const std::vector<PassSeg>& segs, bool packed, hip
   }
   LLM_HIP_RET(hipMemcpyAsync(pmeta.p, meta.data(), ((size_t)4 * CAP + 4 * ntile) * sizeof(int32_t),
                              hipMemcpyHostToDevice, st));
+  std::vector<int32_t> targets;
+  if (scoring) {  // each packed row's next token of its own sequence (maybe the next pass's)
+    for (const PassSeg& s : segs)
+      for (int i = 0; i < s.len; ++i) targets.push_back(scoring->seq[s.row][s.p0 + i + 1]);
+    LLM_HIP_RET(hipMemcpyAsync(pmeta.p + 8 * CAP, targets.data(), (size_t)m * sizeof(int32_t),
+                               hipMemcpyHostToDevice, st));
+  }
   Rows R;
   R.n = m;
   R.x = px.p; R.q = pq.p; R.o = po.p; R.h1 = ph1.p; R.act = pact.p; R.sa = psa.p;
@@ -115,11 +122,28 @@ int llm_decoder::prefill_pass(const std::vector<PassSeg>& segs, bool packed, hip
     RET_IF(layer_attn(l, st, R));
     RET_IF(layer_post(l, st, R));
   }
+  if (scoring) {
+    const int32_t* tg = pmeta.p + 8 * CAP;
+    if (score_form == 0) {
+      LLM_HIP_RET(launch_lm_head_logprobs(px.p, emb_packed.p, tg, lp_val.p, nullptr, m, V, hid,
+                                          lp_ws.p, st));
+    } else if (score_form == 1) {
+      LLM_HIP_RET(launch_lm_head(px.p, emb_packed.p, lp_logits.p, m, V, hid, nullptr, nullptr, st));
+      LLM_HIP_RET(launch_logprob_rows(lp_logits.p, m, V, tg, 0, lp_val.p, nullptr, nullptr, nullptr,
+                                      st));
+    }
+    LLM_HIP_RET(hipMemcpyAsync(h_lp.data(), lp_val.p, (size_t)m * sizeof(float),
+                               hipMemcpyDeviceToHost, st));
+  }
   int q0 = 0;
   for (int j = 0; j < nseg; ++j) {
     const PassSeg& s = segs[j];
     const int last = q0 + s.len - 1;
     h_pos[s.row] = s.p0 + s.len;
+    if (scoring) {  // (no token choice: the rows are released when the group is scored)
+      q0 += s.len;
+      continue;
+    }
     // (serving: the step that follows takes its token and positions from the
     // host -- serve_step -- so an admission pays no LM head)
     if (s.last && !serving) {  // the row's last token: logits -> its next token, decode state
@@ -134,6 +158,13 @@ int llm_decoder::prefill_pass(const std::vector<PassSeg>& segs, bool packed, hip
     q0 += s.len;
   }
   LLM_HIP_RET(hipStreamSynchronize(st));  // meta / pc are this pass's staging
+  if (scoring) {
+    q0 = 0;
+    for (const PassSeg& s : segs) {
+      for (int i = 0; i < s.len; ++i) scoring->out[s.row][s.p0 + i + 1] = h_lp[q0 + i];
+      q0 += s.len;
+    }
+  }
   return LLM_OK;
 }
 

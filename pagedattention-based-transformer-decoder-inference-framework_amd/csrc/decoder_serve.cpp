@@ -2,6 +2,7 @@
 // admitted, which row a request holds and which row moves at a retirement;
 // this file executes those decisions on the pages, the rows' device state and
 // the step (decoder_step.cpp run_step).
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 #include <string>
@@ -83,7 +84,18 @@ int llm_decoder::serve_step(float* logits_dev, llm_serve_event* events, int* n_e
     if (packed_prefill) RET_IF(prefill_rows(prow.data(), ptok.data(), plen.data(), na, stream));
   }
   if (serve_dirty) RET_IF(serve_upload());
-  for (int r = 0; r < live; ++r) hs_tok[r] = requests.at(plan.row(r).id).feed;
+  bool ask = false;
+  for (int r = 0; r < live; ++r) {
+    const ServeRequest& rq = requests.at(plan.row(r).id);
+    hs_tok[r] = rq.feed;
+    hl_topn[r] = rq.top_logprobs;
+    ask = ask || rq.top_logprobs >= 0;
+  }
+  hl_n = live;
+  if (ask != step_logprobs) {
+    step_logprobs = ask;
+    drop_step_graph();  // the logprob_rows launch joins / leaves the step
+  }
   const bool new_graph = use_graph && graph_batch != batch;  // (run_step instantiates then)
   const int rc = run_step(hs_tok.data(), logits_dev, hs_next.data(), stream);
   if (rc != LLM_ERR_RANGE) RET_IF(rc);  // (a clamped step still produced its ids)
@@ -137,6 +149,15 @@ extern "C" int llm_decoder_serve_begin(llm_decoder* d) {
   d->hs_temp.assign(B, 0.f); d->hs_topp.assign(B, 1.f); d->hs_topk.assign(B, 0);
   d->hs_seed.assign(B, 0); d->hs_pos.assign(B, 0); d->hs_ctx.assign(B, 1);
   d->hs_tok.assign(B, 0); d->hs_next.assign(B, 0);
+  if (!d->sl_chosen.p) {
+    RET_IF(d->sl_chosen.alloc(B));
+    RET_IF(d->sl_top_lp.alloc(B * LLM_MAX_TOP_LOGPROBS));
+    RET_IF(d->sl_top_id.alloc(B * LLM_MAX_TOP_LOGPROBS));
+  }
+  d->hl_chosen.assign(B, 0.f); d->hl_top_lp.assign(B * LLM_MAX_TOP_LOGPROBS, 0.f);
+  d->hl_top_id.assign(B * LLM_MAX_TOP_LOGPROBS, 0); d->hl_topn.assign(B, -1);
+  d->hl_n = 0;
+  d->step_logprobs = false;
   ServeGeom geom;
   geom.max_rows = d->maxB;
   geom.num_pages = kv_cache_num_pages(d->kv);
@@ -160,16 +181,16 @@ extern "C" int llm_decoder_serve_end(llm_decoder* d) {
   d->plan.begin(d->plan.geom());
   d->requests.clear();
   d->serving = false;
+  d->step_logprobs = false;
+  d->hl_n = 0;
   d->drop_step_graph();
   d->batch = 0;
   d->h_pos.assign(d->maxB, 0);
   return kv_cache_clear(d->kv);
 }
 
-extern "C" int llm_decoder_submit(llm_decoder* d, const int32_t* prompt, int n,
-                                  const llm_request_options* opt, long long* id) {
-  LLM_REQUIRE(d && prompt && opt && id, "llm_decoder_submit: NULL");
-  std::lock_guard<std::mutex> g(d->mu);
+static int submit_request(llm_decoder* d, const int32_t* prompt, int n,
+                          const llm_request_options* opt, int top_logprobs, long long* id) {
   LLM_REQUIRE(d->serving, "llm_decoder_submit: not serving (llm_decoder_serve_begin first)");
   LLM_REQUIRE(n >= 1, "llm_decoder_submit: a prompt needs >= 1 token");
   LLM_REQUIRE(opt->max_new_tokens >= 1, "llm_decoder_submit: max_new_tokens must be >= 1");
@@ -191,7 +212,40 @@ extern "C" int llm_decoder_submit(llm_decoder* d, const int32_t* prompt, int n,
   rq.prompt.assign(prompt, prompt + n);
   rq.opt = *opt;
   rq.feed = prompt[n - 1];
+  rq.top_logprobs = top_logprobs;
   *id = rid;
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_submit(llm_decoder* d, const int32_t* prompt, int n,
+                                  const llm_request_options* opt, long long* id) {
+  LLM_REQUIRE(d && prompt && opt && id, "llm_decoder_submit: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  return submit_request(d, prompt, n, opt, -1, id);
+}
+
+extern "C" int llm_decoder_submit_logprobs(llm_decoder* d, const int32_t* prompt, int n,
+                                           const llm_request_options* opt, int top_logprobs,
+                                           long long* id) {
+  LLM_REQUIRE(d && prompt && opt && id, "llm_decoder_submit_logprobs: NULL");
+  LLM_REQUIRE(top_logprobs >= 0 && top_logprobs <= LLM_MAX_TOP_LOGPROBS,
+              "llm_decoder_submit_logprobs: top_logprobs must be in [0, 8]");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->V >= LLM_MAX_TOP_LOGPROBS,
+              "llm_decoder_submit_logprobs: vocab_size < 8 (the step takes the rows' top 8)");
+  return submit_request(d, prompt, n, opt, top_logprobs, id);
+}
+
+extern "C" int llm_decoder_serve_logprobs(llm_decoder* d, float* chosen_lp, float* top_lp,
+                                          int32_t* top_id, int32_t* top_n) {
+  LLM_REQUIRE(d, "llm_decoder_serve_logprobs: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_REQUIRE(d->serving, "llm_decoder_serve_logprobs: not serving");
+  const size_t n = (size_t)d->hl_n, nt = n * LLM_MAX_TOP_LOGPROBS;
+  if (chosen_lp) std::copy(d->hl_chosen.begin(), d->hl_chosen.begin() + n, chosen_lp);
+  if (top_lp) std::copy(d->hl_top_lp.begin(), d->hl_top_lp.begin() + nt, top_lp);
+  if (top_id) std::copy(d->hl_top_id.begin(), d->hl_top_id.begin() + nt, top_id);
+  if (top_n) std::copy(d->hl_topn.begin(), d->hl_topn.begin() + n, top_n);
   return LLM_OK;
 }
 

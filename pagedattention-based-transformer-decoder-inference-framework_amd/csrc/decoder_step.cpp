@@ -339,6 +339,11 @@ int llm_decoder::next_tokens(const float* xr, int n, int r0, const int32_t* ctr,
                                lm_pi.p + (size_t)r0 * lm_nwg, st));
     LLM_HIP_RET(launch_sample_each(lg, n, V, sv_temp.p + r0, sv_topk.p + r0, sv_topp.p + r0,
                                    sv_seed.p + r0, ctr, tokens.p + r0, st));
+    if (step_logprobs)  // a live request asked: every live row's, by constants of the step
+      LLM_HIP_RET(launch_logprob_rows(lg, n, V, tokens.p + r0, LLM_MAX_TOP_LOGPROBS,
+                                      sl_chosen.p + r0,
+                                      sl_top_lp.p + (size_t)r0 * LLM_MAX_TOP_LOGPROBS,
+                                      sl_top_id.p + (size_t)r0 * LLM_MAX_TOP_LOGPROBS, nullptr, st));
     if (adv_pos) LLM_HIP_RET(launch_advance(adv_pos, adv_ctx, n, st));
     return LLM_OK;
   }
@@ -427,6 +432,15 @@ int llm_decoder::run_step(const int32_t* tokens_host, float* logits_dev, int32_t
     LLM_HIP_RET(hipMemcpyAsync(h_cand.data() + 2 * batch, cand_parent.p, nb,
                                hipMemcpyDeviceToHost, st));
     LLM_HIP_RET(hipMemcpyAsync(h_cand.data() + 4 * batch, cand_token.p, nb,
+                               hipMemcpyDeviceToHost, st));
+  }
+  if (serving && step_logprobs) {  // (complete with the synchronisation below)
+    const size_t nt = (size_t)batch * LLM_MAX_TOP_LOGPROBS;
+    LLM_HIP_RET(hipMemcpyAsync(hl_chosen.data(), sl_chosen.p, sizeof(float) * batch,
+                               hipMemcpyDeviceToHost, st));
+    LLM_HIP_RET(hipMemcpyAsync(hl_top_lp.data(), sl_top_lp.p, sizeof(float) * nt,
+                               hipMemcpyDeviceToHost, st));
+    LLM_HIP_RET(hipMemcpyAsync(hl_top_id.data(), sl_top_id.p, sizeof(int32_t) * nt,
                                hipMemcpyDeviceToHost, st));
   }
   if (next_host) {

@@ -25,11 +25,18 @@
 // The epilogue writes the logits and a per-(row, workgroup) (max, first
 // index) pair; argmax_partials_kernel reduces those pairs per row (first
 // maximum wins), so greedy decoding never re-reads the [M][V] logits.
+//
+// lm_head_logprobs (scoring) is lm_head_kernel's LP form: the epilogue writes
+// no logits but a per-(row, workgroup) {max, sum exp(x - max), target logit}
+// partial, and logprob_merge_kernel reduces those per row to the target's
+// log-probability (x_t - m) - log(s + 1e-6).  The LP forms use the same 100 /
+// 104 / 124 VGPRs, no scratch, and one more LDS row per partial array.
 #include "common.hpp"
 #include "row_ops.hpp"
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace llm {
 
@@ -59,16 +66,37 @@ struct LmHeadArgs {
              // E loads; bit3: E with the default cache policy (kept) instead of nt
 };
 
+// lm_head_logprobs' operands (the LP form of lm_head_kernel): per (row,
+// workgroup) partials of the row's log-softmax instead of logits.
+struct LmLogprobArgs : LmHeadArgs {
+  const int32_t* targets;  // [M]; outside [0, V): ignore index
+  float* part_m;           // [M][nwg] max over the workgroup's vocabulary range
+  float* part_s;           // [M][nwg] sum exp(x - that max)
+  float* part_t;           // [M][nwg] the target's logit if it lies in the range, else 0
+};
+
 // MT = 16-row tiles of x per workgroup (1, 2 or 4); WAVES waves, each NTW
 // vocabulary tiles (16 rows of E) per k-step against one read of the x
 // fragments from LDS.
-template <int MT, int WAVES, int NTW>
-__global__ __launch_bounds__(WAVES * 64) void lm_head_kernel(LmHeadArgs a) {
+// Args = LmLogprobArgs is the LP form (lm_head_logprobs): the same staging,
+// loads and MFMA sequence, so the same logits in registers bit for bit, reduced
+// to LmLogprobArgs' partials; no logits are written.  A compile-time form, not
+// a branch in the existing instantiations: <4, 16, 1> sits at 124 of its 128
+// VGPRs.
+template <int MT, int WAVES, int NTW, typename Args = LmHeadArgs>
+__global__ __launch_bounds__(WAVES * 64) void lm_head_kernel(Args a) {
+  constexpr bool LP = std::is_same_v<Args, LmLogprobArgs>;
   constexpr int kLmThreads = WAVES * 64;
+  constexpr int kTiles = WAVES * NTW;
   // A fragments of the chunk: [mt][ks][hi/lo][64 lanes] x 16 B
   __shared__ __attribute__((aligned(16))) u32x4 xa[MT][kLmKs][2][64];
-  __shared__ float pv[WAVES * NTW][16 * MT];
-  __shared__ int pi[WAVES * NTW][16 * MT];
+  // LP: pv the tiles' maxima, pi their sums (float bits); row kTiles: the
+  // target's logit and whether a lane of this workgroup held it
+  __shared__ float pv[kTiles + (LP ? 1 : 0)][16 * MT];
+  __shared__ int pi[kTiles + (LP ? 1 : 0)][16 * MT];
+  if constexpr (LP) {  // (ordered before the epilogue by the chunks' barriers)
+    if (threadIdx.x < 16 * MT) { pv[kTiles][threadIdx.x] = 0.f; pi[kTiles][threadIdx.x] = 0; }
+  }
   const int lane = lane_id();
   const int w = wave_id_uniform();
   const int m0 = blockIdx.y * 16 * MT;
@@ -194,6 +222,47 @@ __global__ __launch_bounds__(WAVES * 64) void lm_head_kernel(LmHeadArgs a) {
   // acc[j][mt] lane l, reg r: x row m0 + mt*16 + 4*(l>>4) + r, vocab row
   // 16 tile_j + (l&15) (C/D layout: col = lane&15 -> here the vocabulary
   // index, row = 4*(lane>>4)+reg).
+  if constexpr (LP) {
+    // Per (row, tile): max and sum exp(x - max) over the tile's 16 lanes
+    // (butterflies: every lane ends with the same bits), and the target's
+    // logit from the one lane of the grid that holds it.
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+      const int t = w * NTW + j;
+      const int n = t < a.tiles ? (blockIdx.x * a.tiles + t) * 16 + (lane & 15) : a.V;
+      const bool in = n < a.V;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = mt * 16 + 4 * (lane >> 4) + r;
+          const float v = acc[j][mt][r];
+          float bm = in ? v : -INFINITY;
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) bm = fmaxf(bm, __shfl_xor(bm, off, 64));
+          float e = in ? expf(v - bm) : 0.f;
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) e += __shfl_xor(e, off, 64);
+          if ((lane & 15) == 0) { pv[t][row] = bm; pi[t][row] = __float_as_int(e); }
+          const int tg = m0 + row < a.M ? a.targets[m0 + row] : -1;
+          if (in && n == tg) { pv[kTiles][row] = v; pi[kTiles][row] = 1; }
+        }
+      }
+    }
+    __syncthreads();
+    for (int row = threadIdx.x; row < 16 * MT; row += kLmThreads) {
+      if (m0 + row >= a.M) continue;
+      float m = pv[0][row];
+      for (int ww = 1; ww < a.tiles; ++ww) m = fmaxf(m, pv[ww][row]);
+      float s = 0.f;  // tiles in increasing vocabulary order (a tile past V: 0 * exp(-inf))
+      for (int ww = 0; ww < a.tiles; ++ww) s += __int_as_float(pi[ww][row]) * expf(pv[ww][row] - m);
+      const size_t o = (size_t)(m0 + row) * a.nwg + blockIdx.x;
+      a.part_m[o] = m;
+      a.part_s[o] = s;
+      a.part_t[o] = pi[kTiles][row] ? pv[kTiles][row] : 0.f;
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < NTW; ++j) {
   const int t = w * NTW + j;
@@ -230,6 +299,42 @@ __global__ __launch_bounds__(WAVES * 64) void lm_head_kernel(LmHeadArgs a) {
       if (pv[ww][row] > bv) { bv = pv[ww][row]; bi = pi[ww][row]; }
     a.part_val[(size_t)(m0 + row) * a.nwg + blockIdx.x] = bv;
     a.part_idx[(size_t)(m0 + row) * a.nwg + blockIdx.x] = bi;
+  }
+}
+
+// Per row: the nwg partials of lm_head_kernel's LP form merged in a fixed order,
+// M = max m_w, S = sum s_w exp(m_w - M), then lse = log(S + 1e-6) and the
+// target's log-probability (x_t - M) - lse (beam_rows_kernel's term).  The
+// target's logit is the partial of the workgroup whose range holds it.
+__global__ __launch_bounds__(256) void logprob_merge_kernel(LmLogprobArgs lp, int nwg,
+                                                            int cols_per_wg, int V,
+                                                            float* __restrict__ logprob,
+                                                            float* __restrict__ stats) {
+  __shared__ float sm[4], ss[4];
+  const int r = blockIdx.x;
+  const float* pm = lp.part_m + (size_t)r * nwg;
+  const float* ps = lp.part_s + (size_t)r * nwg;
+  float m = -INFINITY;
+  for (int j = threadIdx.x; j < nwg; j += 256) m = fmaxf(m, pm[j]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+  float s = 0.f;
+  for (int j = threadIdx.x; j < nwg; j += 256) s += ps[j] * expf(pm[j] - m);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) ss[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+    const float lse = logf(s + 1e-6f);
+    const int tg = lp.targets[r];
+    const bool valid = tg >= 0 && tg < V;
+    const float xt = valid ? lp.part_t[(size_t)r * nwg + tg / cols_per_wg] : 0.f;
+    logprob[r] = valid ? (xt - m) - lse : 0.f;
+    if (stats) { stats[3 * r] = m; stats[3 * r + 1] = lse; stats[3 * r + 2] = xt; }
   }
 }
 
@@ -481,6 +586,31 @@ hipError_t launch_lm_head(const float* x, const void* E, float* logits, int M, i
   return hipGetLastError();
 }
 
+size_t lm_head_logprobs_ws_floats(int M, int V) { return (size_t)3 * M * lm_head_workgroups(V); }
+
+// The LM head with the log-softmax epilogue: two launches (partials, merge), no
+// [M][V] logits anywhere.  ws: lm_head_logprobs_ws_floats(M, V) floats.  M <= 16
+// takes lm_head_kernel<1, 16, 1>'s form (lm_head_x1_kernel's logits bit for bit).
+hipError_t launch_lm_head_logprobs(const float* x, const void* E, const int32_t* targets,
+                                   float* logprob, float* stats, int M, int V, int K, float* ws,
+                                   hipStream_t st) {
+  const int nwg = lm_head_workgroups(V);
+  const size_t n = (size_t)M * nwg;
+  LmLogprobArgs a{{x, static_cast<const _Float16*>(E), nullptr, nullptr, nullptr, M, V, K, nwg,
+                   lm_head_tiles(V), 0},
+                  targets, ws, ws + n, ws + 2 * n};
+  const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+  const dim3 grid(a.nwg, (M + 16 * mt - 1) / (16 * mt));
+  if (mt == 1) hipLaunchKernelGGL((lm_head_kernel<1, 16, 1, LmLogprobArgs>), grid, dim3(1024), 0, st, a);
+  else if (mt == 2) hipLaunchKernelGGL((lm_head_kernel<2, 16, 1, LmLogprobArgs>), grid, dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL((lm_head_kernel<4, 16, 1, LmLogprobArgs>), grid, dim3(1024), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(logprob_merge_kernel, dim3(M), dim3(256), 0, st, a, a.nwg, a.tiles * 16, V,
+                     logprob, stats);
+  return hipGetLastError();
+}
+
 hipError_t launch_argmax_partials(const float* part_val, const int32_t* part_idx, int M, int nwg,
                                   int32_t* out, hipStream_t st, int32_t* pos, int32_t* ctx) {
   hipLaunchKernelGGL(argmax_partials_kernel, dim3(M), dim3(256), 0, st, part_val, part_idx, nwg,
@@ -507,5 +637,29 @@ extern "C" int lm_head(const float* x, const void* E, float* logits, int M, int 
   if (e == hipSuccess) e = launch_lm_head(x, P, logits, M, V, K, nullptr, nullptr, st);
   (void)hipFreeAsync(P, st);
   if (e != hipSuccess) return fail(LLM_ERR_HIP, std::string("lm_head: ") + hipGetErrorString(e));
+  return LLM_OK;
+}
+
+extern "C" int lm_head_logprobs(const float* x, const void* E, const int32_t* targets,
+                                float* logprob, float* stats, int M, int V, int K, void* stream) {
+  LLM_REQUIRE(M >= 0 && V > 0 && K > 0, "lm_head_logprobs: bad M/V/K");
+  if (M == 0) return LLM_OK;
+  LLM_REQUIRE(x && E && targets && logprob, "lm_head_logprobs: NULL operand");
+  LLM_REQUIRE(K % 32 == 0, "lm_head_logprobs: K must be a multiple of 32");
+  LLM_REQUIRE(lm_head_packed_bytes(V, K) < 0xFFFFFFF0ull,
+              "lm_head_logprobs: E too large for 32-bit offsets");
+  // one-shot entry, as lm_head: a scratch copy of E packed, and the partials
+  hipStream_t st = as_stream(stream);
+  void* P = nullptr;
+  float* ws = nullptr;
+  LLM_HIP_RET(hipMallocAsync(&P, lm_head_packed_bytes(V, K), st));
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&ws),
+                                lm_head_logprobs_ws_floats(M, V) * sizeof(float), st);
+  if (e == hipSuccess) e = launch_lm_pack(E, P, V, K, st);
+  if (e == hipSuccess) e = launch_lm_head_logprobs(x, P, targets, logprob, stats, M, V, K, ws, st);
+  if (ws) (void)hipFreeAsync(ws, st);
+  (void)hipFreeAsync(P, st);
+  if (e != hipSuccess)
+    return fail(LLM_ERR_HIP, std::string("lm_head_logprobs: ") + hipGetErrorString(e));
   return LLM_OK;
 }

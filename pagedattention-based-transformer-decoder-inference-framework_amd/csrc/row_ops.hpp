@@ -39,6 +39,18 @@ hipError_t launch_lm_head(const float* x, const void* E, float* logits, int M, i
 hipError_t launch_argmax_partials(const float* part_val, const int32_t* part_idx, int M, int nwg,
                                   int32_t* out, hipStream_t st, int32_t* pos = nullptr,
                                   int32_t* ctx = nullptr);
+// The LM head with a log-softmax epilogue (lm_head_logprobs in llm_decoder.h)
+// over a packed E: the partials launch and the merge launch on `st`, both
+// capturable.  ws: device scratch of lm_head_logprobs_ws_floats(M, V) floats.
+size_t lm_head_logprobs_ws_floats(int M, int V);
+hipError_t launch_lm_head_logprobs(const float* x, const void* E, const int32_t* targets,
+                                   float* logprob, float* stats, int M, int V, int K, float* ws,
+                                   hipStream_t st);
+// Chosen and top-n log-probabilities of materialised rows (csrc/logprobs.hip,
+// logprob_rows in llm_decoder.h); one launch, capturable.
+hipError_t launch_logprob_rows(const float* logits, int rows, int V, const int32_t* chosen,
+                               int top_n, float* chosen_lp, float* top_lp, int32_t* top_id,
+                               float* stats, hipStream_t st);
 // Device sampling (csrc/sample.hip); counter[r] is the per-row draw counter.
 hipError_t launch_sample(const float* logits, int rows, int row0, int V, float temperature,
                          int top_k, float top_p, uint64_t seed, const int32_t* counter,

@@ -103,6 +103,7 @@ class LlmBeamOptions(ctypes.Structure):
 
 
 LLM_FINISH_EOS, LLM_FINISH_LENGTH = 1, 2
+LLM_MAX_TOP_LOGPROBS = 8
 
 
 class LlmRequestOptions(ctypes.Structure):
@@ -193,6 +194,10 @@ _SIGS = {
     "f16_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                          c_int, c_void_p]),
     "lm_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "lm_head_logprobs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_void_p]),
+    "logprob_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p]),
     "argmax_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sample_rows": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, ctypes.c_uint64,
                             c_int, c_void_p, c_void_p]),
@@ -204,6 +209,13 @@ _SIGS = {
     "llm_decoder_serve_end": (c_int, [c_void_p]),
     "llm_decoder_submit": (c_int, [c_void_p, c_i32p, c_int, ctypes.POINTER(LlmRequestOptions),
                                    ctypes.POINTER(c_ll)]),
+    "llm_decoder_submit_logprobs": (c_int, [c_void_p, c_i32p, c_int,
+                                            ctypes.POINTER(LlmRequestOptions), c_int,
+                                            ctypes.POINTER(c_ll)]),
+    "llm_decoder_serve_logprobs": (c_int, [c_void_p, ctypes.POINTER(c_float),
+                                           ctypes.POINTER(c_float), c_i32p, c_i32p]),
+    "llm_decoder_score": (c_int, [c_void_p, c_i32p, c_i32p, c_int, c_int,
+                                  ctypes.POINTER(c_float)]),
     "llm_decoder_cancel": (c_int, [c_void_p, c_ll]),
     "llm_decoder_serve_step": (c_int, [c_void_p, c_void_p, ctypes.POINTER(LlmServeEvent), c_int,
                                        ctypes.POINTER(c_int)]),
@@ -724,6 +736,37 @@ def lm_head(x, E, stream=None):
     out = torch.empty((M, V), dtype=torch.float32, device=x.device)
     check(lib.lm_head(ptr(x), ptr(E), ptr(out), M, V, K, stream_ptr(stream)))
     return out
+
+
+def lm_head_logprobs(x, E, targets, want_stats=True, stream=None):
+    """lm_head_logprobs on torch device tensors: x fp32 [M][K], E fp16 [V][K],
+    targets int32 [M] -> (logprob [M], stats [M][3] = {m, lse, x_target} or None)."""
+    import torch
+    lib = load()
+    M, K = x.shape
+    V = E.shape[0]
+    lp = torch.empty((M,), dtype=torch.float32, device=x.device)
+    stats = torch.empty((M, 3), dtype=torch.float32, device=x.device) if want_stats else None
+    check(lib.lm_head_logprobs(ptr(x), ptr(E), ptr(targets), ptr(lp), ptr(stats), M, V, K,
+                               stream_ptr(stream)))
+    return lp, stats
+
+
+def logprob_rows(logits, chosen=None, top_n=0, want_stats=True, stream=None):
+    """logprob_rows on torch device tensors: fp32 logits [R][V], chosen int32 [R]
+    or None -> (chosen_lp [R] or None, top_lp [R][top_n], top_id [R][top_n],
+    stats [R][2] = {m, lse} or None)."""
+    import torch
+    lib = load()
+    R, V = logits.shape
+    dev = logits.device
+    clp = torch.empty((R,), dtype=torch.float32, device=dev) if chosen is not None else None
+    tlp = torch.empty((R, top_n), dtype=torch.float32, device=dev)
+    tid = torch.empty((R, top_n), dtype=torch.int32, device=dev)
+    stats = torch.empty((R, 2), dtype=torch.float32, device=dev) if want_stats else None
+    check(lib.logprob_rows(ptr(logits), R, V, ptr(chosen), top_n, ptr(clp), ptr(tlp), ptr(tid),
+                           ptr(stats), stream_ptr(stream)))
+    return clp, tlp, tid, stats
 
 
 def argmax_rows(logits, stream=None):
