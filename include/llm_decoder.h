@@ -518,6 +518,27 @@ int kv_cache_fork(kv_cache* c, int src_beam, int dst_beam);
 int kv_cache_reorder(kv_cache* c, int first_beam, int n, const int32_t* parent, int n_tokens);
 /* Release every page of `beam` (refcount-aware). */
 int kv_cache_release(kv_cache* c, int beam);
+/* Blocks that outlive a row (what a prefix cache is made of).  A block is
+ * tile `tile` of a beam across all layers and heads: num_layers * num_heads
+ * pages, listed layer-major, head-minor (pages[layer * num_heads + head]).
+ *   hold    every (layer, head) entry of the tile must be mapped, else
+ *           LLM_ERR_INVALID with nothing changed.  Writes the page ids and
+ *           takes one more reference on each page: they stay allocated, with
+ *           their contents, after kv_cache_release(beam).
+ *   attach  every (layer, head) entry of the tile must be -1 and every page
+ *           allocated, else LLM_ERR_INVALID with nothing changed.  The entries
+ *           become those pages, plus one reference each, as any other table
+ *           write (pushed by the next kv_cache_sync; a release mark above the
+ *           tile falls to it; the entries are no LRU candidates).  A later
+ *           append into the tile copies on write, as after kv_cache_fork.
+ *   drop    one reference less on each page; a page whose count reaches 0
+ *           returns to its zone's free list.  LLM_ERR_INVALID with nothing
+ *           changed if a page is not allocated.
+ * kv_cache_clear (and a snapshot load) resets every count: a holder must
+ * forget its page lists then, and never drop them afterwards. */
+int kv_cache_hold_tile(kv_cache* c, int beam, int tile, int32_t* pages);
+int kv_cache_attach_tile(kv_cache* c, int beam, int tile, const int32_t* pages);
+int kv_cache_drop_pages(kv_cache* c, const int32_t* pages);
 /* Release the pages of `beam` that lie wholly below token n_tokens: tiles
  * < n_tokens / page_size, all layers and heads (refcount-aware: a page a
  * forked beam still shares stays allocated until its last owner lets go).
@@ -848,8 +869,60 @@ typedef struct llm_serve_event {
  * _set_rope, _set_kv_scales, _set_packed_prefill and _set_taps return
  * LLM_ERR_INVALID. */
 int llm_decoder_serve_begin(llm_decoder* d);
+/* llm_decoder_serve_begin with options (llm_decoder_serve_begin is this call
+ * with every option 0).
+ * prefix_cache != 0: for the length of this session -- until
+ * llm_decoder_serve_end -- prompt blocks outlive the rows that computed them,
+ * and a request whose prompt begins with cached blocks is not prefilled over
+ * them (csrc/serve_plan.hpp, csrc/prefix_cache.hpp).  A block is page_size
+ * consecutive prompt positions from a multiple of page_size on, over all
+ * layers and heads (kv_cache_hold_tile); two prompts share it exactly when
+ * they agree on every token id up to its end.
+ *   hit      a prompt of n tokens prefills n - 1 positions and hits at most
+ *            floor((n - 1) / page_size) blocks: the longest cached chain from
+ *            its start.  At admission those pages are attached to its row
+ *            (kv_cache_attach_tile), the row starts at hit_blocks * page_size
+ *            and prompt[hit_blocks * page_size : n - 1] is prefilled -- maybe
+ *            nothing.  Nothing ever appends into a shared tile, so no page is
+ *            copied on write;
+ *   publish  after its admission prefill a new row publishes the full tiles
+ *            it computed, up to the first whose block is cached already.
+ *            Generated tokens are not published;
+ *   step     admission ends before a head whose first uncached block a
+ *            request admitted earlier in the same step will publish; it
+ *            enters at the next step with the hit (counted as a deferral);
+ *   pages    committed_pages = the live requests' private needs +
+ *            num_layers * num_heads per block in use; a request's private
+ *            need is its need less its hit blocks', less what it published.
+ *            Cached blocks nobody uses hold idle_pages.  committed_pages +
+ *            idle_pages <= num_pages at all times: before the head is
+ *            admitted, idle blocks are evicted (those without a cached child,
+ *            least recently used first; kv_cache_drop_pages) until that
+ *            holds with it, and it waits if evicting all would not do.  So no
+ *            step of an admitted request returns LLM_ERR_OOM.  A submit is
+ *            still checked against the whole pool with its full need.
+ * Composes with both weight types, fp16 / LLM_FP8 pages, rope and packed
+ * prefill; LLM_ERR_UNSUPPORTED with a sliding window set (its page release
+ * and its charge do not compose with held blocks).  LLM_ERR_INVALID for an
+ * option that is neither 0 nor 1. */
+typedef struct llm_serve_options {
+  int prefix_cache;  /* 0 (off) or 1 */
+} llm_serve_options;
+int llm_decoder_serve_begin_opts(llm_decoder* d, const llm_serve_options* opt);
+/* The prefix cache's counters for the current session; all 0 outside a
+ * session begun with prefix_cache. */
+typedef struct llm_prefix_stats {
+  long long positions_due;   /* the sum of n - 1 over the admitted requests */
+  long long positions_hit;   /* ... of which served from cached blocks */
+  long long cached_blocks;   /* blocks cached now, used or idle */
+  long long idle_pages;      /* pages of the cached blocks nobody uses */
+  long long evicted_blocks;  /* blocks evicted so far */
+  long long deferrals;       /* admissions ended by the same-step rule */
+} llm_prefix_stats;
+int llm_decoder_serve_prefix_stats(const llm_decoder* d, llm_prefix_stats* out);
 /* Leave serving mode: every request, waiting or live, is dropped without an
- * event, the cache is cleared and no rows stay active (batch 0).
+ * event, the cache is cleared (a prefix cache's blocks with it) and no rows
+ * stay active (batch 0).
  * LLM_ERR_INVALID if not serving. */
 int llm_decoder_serve_end(llm_decoder* d);
 /* Queue a request of n >= 1 prompt ids (host; copied); *id receives its id
@@ -907,7 +980,7 @@ int llm_decoder_cancel(llm_decoder* d, long long id);
 int llm_decoder_serve_step(llm_decoder* d, float* logits_dev, llm_serve_event* events, int cap,
                            int* n_events);
 /* *live / *waiting requests, *committed_pages (the sum of the live requests'
- * needs) and *graph_instantiations (step graphs instantiated by serving
+ * needs; with a prefix cache, of their private needs and the blocks in use) and *graph_instantiations (step graphs instantiated by serving
  * steps since the decoder was created).  Any pointer may be
  * NULL; valid outside serving mode too (0 live, 0 waiting). */
 int llm_decoder_serve_stats(const llm_decoder* d, int* live, int* waiting,

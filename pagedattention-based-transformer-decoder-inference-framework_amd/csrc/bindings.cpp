@@ -303,9 +303,12 @@ class Decoder {
 
   // Continuous batching (llm_decoder_serve_*): submit at any time, one
   // serve_step = admissions + their prefill + one decode step of all live rows
-  void serve_begin() {
+  // prefix_cache: prompt blocks are shared between the session's requests
+  // (llm_decoder_serve_begin_opts)
+  void serve_begin(bool prefix_cache) {
     py::gil_scoped_release nogil;
-    check(llm_decoder_serve_begin(d_));
+    const llm_serve_options o{prefix_cache ? 1 : 0};
+    check(llm_decoder_serve_begin_opts(d_, &o));
   }
   void serve_end() {
     py::gil_scoped_release nogil;
@@ -395,14 +398,27 @@ class Decoder {
     s["graph_instantiations"] = inst;
     return s;
   }
+  // {positions_due, positions_hit, cached_blocks, idle_pages, evicted_blocks,
+  // deferrals} of the session's prefix cache (zeros without one)
+  py::dict serve_prefix_stats() const {
+    llm_prefix_stats p{};
+    check(llm_decoder_serve_prefix_stats(d_, &p));
+    py::dict s;
+    s["positions_due"] = p.positions_due; s["positions_hit"] = p.positions_hit;
+    s["cached_blocks"] = p.cached_blocks; s["idle_pages"] = p.idle_pages;
+    s["evicted_blocks"] = p.evicted_blocks; s["deferrals"] = p.deferrals;
+    return s;
+  }
   // Any number of prompts through the serve loop: the generated ids per prompt
   // in submission order (EOS included where hit).  max_new_tokens: one int or
   // one per prompt; prompt i draws with seed + i.
   // logprobs (None, or 0 .. 8): with it the result is (ids, logprobs), logprobs
-  // per prompt one serve_logprobs entry per generated token.
+  // per prompt one serve_logprobs entry per generated token.  prefix_cache: as
+  // serve_begin's.
   py::object generate_many(const std::vector<std::vector<int32_t>>& prompts,
                            py::object max_new_tokens, int eos_token_id, float temperature,
-                           int top_k, float top_p, uint64_t seed, py::object logprobs) {
+                           int top_k, float top_p, uint64_t seed, py::object logprobs,
+                           bool prefix_cache) {
     const bool want_lp = !logprobs.is_none();
     const int top_lp = want_lp ? logprobs.cast<int>() : -1;
     const size_t B = (size_t)std::max(cfg_.max_batch, 1);
@@ -435,7 +451,8 @@ class Decoder {
     std::vector<llm_serve_event> ev((size_t)std::max(cfg_.max_batch, 1));
     {
     py::gil_scoped_release nogil;
-    check(llm_decoder_serve_begin(d_));
+    const llm_serve_options so{prefix_cache ? 1 : 0};
+    check(llm_decoder_serve_begin_opts(d_, &so));
     int rc = LLM_OK, range_rc = LLM_OK;
     for (size_t i = 0; i < n && rc == LLM_OK; ++i) {
       llm_request_options o{max_new[i], eos_token_id, temperature, top_k, top_p, seed + i};
@@ -815,7 +832,7 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def_property("packed_prefill", &Decoder::packed_prefill, &Decoder::set_packed_prefill)
         .def("set_sampling", &Decoder::set_sampling, py::arg("temperature"),
              py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("seed") = 0)
-        .def("serve_begin", &Decoder::serve_begin)
+        .def("serve_begin", &Decoder::serve_begin, py::arg("prefix_cache") = false)
         .def("submit", &Decoder::submit, py::arg("tokens"), py::arg("max_new_tokens"),
              py::arg("eos_token_id") = -1, py::arg("temperature") = 0.0f, py::arg("top_k") = 0,
              py::arg("top_p") = 1.0f, py::arg("seed") = 0, py::arg("logprobs") = py::none())
@@ -824,11 +841,13 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("cancel", &Decoder::cancel, py::arg("id"))
         .def("serve_step", &Decoder::serve_step, py::arg("logits_ptr") = 0)
         .def("serve_stats", &Decoder::serve_stats)
+        .def("serve_prefix_stats", &Decoder::serve_prefix_stats)
         .def("serve_end", &Decoder::serve_end)
         .def("generate_many", &Decoder::generate_many, py::arg("prompts"),
              py::arg("max_new_tokens"), py::arg("eos_token_id") = -1,
              py::arg("temperature") = 0.0f, py::arg("top_k") = 0, py::arg("top_p") = 1.0f,
-             py::arg("seed") = 0, py::arg("logprobs") = py::none())
+             py::arg("seed") = 0, py::arg("logprobs") = py::none(),
+             py::arg("prefix_cache") = false)
         .def("begin_beams", &Decoder::begin_beams, py::arg("num_seqs"), py::arg("beam_width"),
              py::arg("shared_len"), py::arg("beam_len"), py::arg("seed") = 0,
              py::arg("shuffle") = true)

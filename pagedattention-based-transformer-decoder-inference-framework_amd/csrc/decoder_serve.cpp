@@ -65,23 +65,36 @@ int llm_decoder::serve_step(float* logits_dev, llm_serve_event* events, int* n_e
   const int before = plan.live(), na = plan.admit(), live = plan.live();
   if (live == 0) return LLM_OK;
   batch = live;
+  // (prefix caching: the blocks the admissions evicted, before anything allocates)
+  for (const ServeEvict& e : plan.evictions()) RET_IF(kv_cache_drop_pages(kv, e.pages.data()));
+  plan.evictions().clear();
   if (na) {
     serve_dirty = true;
-    // prompt[:-1] of the new rows, as prefill_prompts chooses
+    // prompt[:-1] of the new rows, as prefill_prompts chooses -- behind the
+    // cached blocks a row hit, whose pages it shares from here on
     std::vector<int32_t> prow, plen, ptok;
     for (int r = before; r < live; ++r) {
-      const std::vector<int32_t>& p = requests.at(plan.row(r).id).prompt;
-      const int n = (int)p.size() - 1;
-      h_pos[r] = 0;
+      const ServeReq& q = plan.row(r);
+      const std::vector<int32_t>& p = requests.at(q.id).prompt;
+      for (int k = 0; k < q.hit_blocks; ++k)
+        RET_IF(kv_cache_attach_tile(kv, r, k, plan.index().block(q.blocks[k]).pages.data()));
+      const int p0 = q.hit_blocks * TS, n = (int)p.size() - 1 - p0;
+      h_pos[r] = p0;
       if (packed_prefill) {
         prow.push_back(r);
         plen.push_back(n);
-        ptok.insert(ptok.end(), p.begin(), p.begin() + n);
+        ptok.insert(ptok.end(), p.begin() + p0, p.begin() + p0 + n);
       } else if (n > 0) {
-        RET_IF(prefill(r, p.data(), n, stream));
+        RET_IF(prefill(r, p.data() + p0, n, stream));
       }
     }
     if (packed_prefill) RET_IF(prefill_rows(prow.data(), ptok.data(), plen.data(), na, stream));
+    // (the tiles' pages are mapped on the host once the prefill has returned;
+    // what reads them later runs behind it on the same stream)
+    for (int r = before; r < live; ++r)
+      RET_IF(plan.publish(r, [&](int tile, int32_t* pages) {
+        return kv_cache_hold_tile(kv, r, tile, pages);
+      }));
   }
   if (serve_dirty) RET_IF(serve_upload());
   bool ask = false;
@@ -118,8 +131,7 @@ int llm_decoder::serve_step(float* logits_dev, llm_serve_event* events, int* n_e
   return LLM_OK;
 }
 
-extern "C" int llm_decoder_serve_begin(llm_decoder* d) {
-  LLM_REQUIRE(d, "llm_decoder_serve_begin: NULL");
+static int serve_begin(llm_decoder* d, bool prefix_cache) {
   std::lock_guard<std::mutex> g(d->mu);
   LLM_REQUIRE(!d->serving, "llm_decoder_serve_begin: already serving");
   LLM_REQUIRE(d->weights_ready, "llm_decoder_serve_begin: weights not loaded");
@@ -130,8 +142,12 @@ extern "C" int llm_decoder_serve_begin(llm_decoder* d) {
   if (d->V > 65536)
     return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin: vocab_size > 65536 (the rows' "
                                      "tokens are chosen by sample_rows_each)");
+  if (prefix_cache && d->window > 0)
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin_opts: prefix_cache with a sliding "
+                                     "window (its page release does not compose with held "
+                                     "blocks)");
   LLM_HIP_RET(hipStreamSynchronize(d->stream));
-  RET_IF(kv_cache_clear(d->kv));
+  RET_IF(kv_cache_clear(d->kv));  // (every page count is reset: plan.begin forgets the blocks)
   d->batch = 0;
   d->row_group = 1;
   d->h_pos.assign(d->maxB, 0);
@@ -165,11 +181,36 @@ extern "C" int llm_decoder_serve_begin(llm_decoder* d) {
   geom.page_size = d->TS;
   geom.window = d->window;
   geom.max_seq_len = d->cfg.max_seq_len;
-  d->plan.begin(geom);
+  d->plan.begin(geom, prefix_cache);
   d->requests.clear();
   d->serve_dirty = false;
   d->serving = true;
   d->drop_step_graph();  // the step's token choice becomes sample_rows_each
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_serve_begin(llm_decoder* d) {
+  LLM_REQUIRE(d, "llm_decoder_serve_begin: NULL");
+  return serve_begin(d, false);
+}
+
+extern "C" int llm_decoder_serve_begin_opts(llm_decoder* d, const llm_serve_options* opt) {
+  LLM_REQUIRE(d && opt, "llm_decoder_serve_begin_opts: NULL");
+  LLM_REQUIRE(opt->prefix_cache == 0 || opt->prefix_cache == 1,
+              "llm_decoder_serve_begin_opts: prefix_cache must be 0 or 1");
+  return serve_begin(d, opt->prefix_cache == 1);
+}
+
+extern "C" int llm_decoder_serve_prefix_stats(const llm_decoder* d, llm_prefix_stats* out) {
+  LLM_REQUIRE(d && out, "llm_decoder_serve_prefix_stats: NULL");
+  std::lock_guard<std::mutex> g(const_cast<llm_decoder*>(d)->mu);
+  const ServePrefixStats& s = d->plan.prefix_stats();
+  out->positions_due = s.due;
+  out->positions_hit = s.hit;
+  out->cached_blocks = d->plan.index().cached_blocks();
+  out->idle_pages = d->plan.idle_pages();
+  out->evicted_blocks = s.evicted;
+  out->deferrals = s.deferrals;
   return LLM_OK;
 }
 
@@ -207,9 +248,12 @@ static int submit_request(llm_decoder* d, const int32_t* prompt, int n,
               "llm_decoder_submit: the request needs " +
                   std::to_string(serve_need(d->plan.geom(), n, opt->max_new_tokens)) +
                   " pages, the pool has " + std::to_string(d->plan.geom().num_pages));
-  const long long rid = d->plan.submit(n, opt->max_new_tokens);
+  // (the plan reads the prompt where the request keeps it: a node of
+  // `requests` stays where it is until the request is erased)
+  std::vector<int32_t> copy(prompt, prompt + n);
+  const long long rid = d->plan.submit(n, opt->max_new_tokens, copy.data());
   llm_decoder::ServeRequest& rq = d->requests[rid];
-  rq.prompt.assign(prompt, prompt + n);
+  rq.prompt = std::move(copy);
   rq.opt = *opt;
   rq.feed = prompt[n - 1];
   rq.top_logprobs = top_logprobs;

@@ -509,6 +509,61 @@ extern "C" int kv_cache_fork(kv_cache* c, int src_beam, int dst_beam) {
   return LLM_OK;
 }
 
+// Blocks that outlive a row (prefix caching): tile `tile` of a beam across
+// all layers and heads, pages[l * H + h].
+extern "C" int kv_cache_hold_tile(kv_cache* c, int beam, int tile, int32_t* pages) {
+  LLM_REQUIRE(c && pages, "kv_cache_hold_tile: NULL");
+  KvCache& k = c->impl;
+  std::lock_guard<std::mutex> g(k.mu);
+  LLM_REQUIRE(k.in_range(0, beam, 0, tile), "kv_cache_hold_tile: bad beam / tile");
+  for (int l = 0; l < k.L; ++l)
+    for (int h = 0; h < k.H; ++h)
+      LLM_REQUIRE(k.h_table[k.index(l, beam, h, tile)] >= 0,
+                  "kv_cache_hold_tile: the tile is not mapped in every layer and head");
+  for (int l = 0; l < k.L; ++l)
+    for (int h = 0; h < k.H; ++h) {
+      const int32_t p = k.h_table[k.index(l, beam, h, tile)];
+      k.refcount[p] += 1;
+      pages[(size_t)l * k.H + h] = p;
+    }
+  return LLM_OK;
+}
+
+extern "C" int kv_cache_attach_tile(kv_cache* c, int beam, int tile, const int32_t* pages) {
+  LLM_REQUIRE(c && pages, "kv_cache_attach_tile: NULL");
+  KvCache& k = c->impl;
+  std::lock_guard<std::mutex> g(k.mu);
+  LLM_REQUIRE(k.in_range(0, beam, 0, tile), "kv_cache_attach_tile: bad beam / tile");
+  for (int l = 0; l < k.L; ++l)
+    for (int h = 0; h < k.H; ++h) {
+      LLM_REQUIRE(k.h_table[k.index(l, beam, h, tile)] < 0,
+                  "kv_cache_attach_tile: the tile has a mapped entry");
+      const int32_t p = pages[(size_t)l * k.H + h];
+      LLM_REQUIRE(p >= 0 && p < k.num_pages && k.refcount[p] > 0,
+                  "kv_cache_attach_tile: not an allocated page");
+    }
+  for (int l = 0; l < k.L; ++l)
+    for (int h = 0; h < k.H; ++h) {
+      const int32_t p = pages[(size_t)l * k.H + h];
+      k.refcount[p] += 1;
+      k.set_entry(k.index(l, beam, h, tile), p);
+    }
+  return LLM_OK;
+}
+
+extern "C" int kv_cache_drop_pages(kv_cache* c, const int32_t* pages) {
+  LLM_REQUIRE(c && pages, "kv_cache_drop_pages: NULL");
+  KvCache& k = c->impl;
+  std::lock_guard<std::mutex> g(k.mu);
+  const size_t n = (size_t)k.L * k.H;
+  for (size_t i = 0; i < n; ++i)
+    LLM_REQUIRE(pages[i] >= 0 && pages[i] < k.num_pages && k.refcount[pages[i]] > 0,
+                "kv_cache_drop_pages: not an allocated page");
+  for (size_t i = 0; i < n; ++i)
+    if (k.refcount[pages[i]] > 0) k.drop_page(pages[i]);  // (a repeated id never takes a count below 0)
+  return LLM_OK;
+}
+
 extern "C" int kv_cache_reorder(kv_cache* c, int first_beam, int n, const int32_t* parent,
                                 int n_tokens) {
   LLM_REQUIRE(c && parent, "kv_cache_reorder: NULL");

@@ -1138,6 +1138,106 @@ extern "C" int serve_plan_sim_tune(const int32_t* prompt_lens, const int32_t* ma
   return count > room ? -(int)count : (int)count;
 }
 
+// Tuning hook: serve_plan_sim_tune with prompts -- the scheduler with its
+// prefix cache (prefix_cache != 0; serve_plan.hpp, prefix_cache.hpp) or without
+// it.  tokens holds the n prompts' ids back to back (prompt_lens[i] each); no
+// window.  out: int64 records (step, kind, id, row, aux, aux2), in the order a
+// serve step produces them -- admissions (each with its evictions before it),
+// the deferral, the publications, the state, tokens, retirements, the state:
+//   kind 0 admit   aux = pages committed after it, aux2 = hit_blocks
+//   kind 1 token, 2 move, 3 retire   as serve_plan_sim_tune, aux2 = 0
+//   kind 4 defer   id = the head that the same-step rule kept waiting, row -1
+//   kind 5 evict   id = the block, row -1, aux = its tile index, aux2 = 0
+//   kind 6 publish id = the request, row = its row, aux = the block, aux2 = its
+//                  tile index
+//   kind 7 state after the step's admissions and publications, kind 8 state
+//          after its retirements: id -1, row -1, aux = committed, aux2 =
+//          idle_pages
+// With the cache off the records of kinds 0 .. 3 are serve_plan_sim_tune's
+// (aux2 = 0).  stats (may be NULL): positions due, positions hit, blocks
+// cached at the end, idle_pages at the end, blocks evicted, deferrals.
+// Returns as serve_plan_sim_tune does.
+extern "C" int serve_prefix_sim_tune(const int32_t* tokens, const int32_t* prompt_lens,
+                                     const int32_t* max_new, const int32_t* gen_lens, int n,
+                                     int max_rows, long long num_pages, int pages_per_tile,
+                                     int page_size, int max_seq_len, int prefix_cache,
+                                     long long* out, int room, long long* stats) {
+  constexpr int kBad = -2147483647 - 1;
+  if (n < 0 || max_rows < 1 || num_pages < 1 || pages_per_tile < 1 || page_size < 1 ||
+      max_seq_len < 1 || room < 0 || (room && !out) || (prefix_cache != 0 && prefix_cache != 1) ||
+      (n && (!tokens || !prompt_lens || !max_new || !gen_lens)))
+    return kBad;
+  for (int i = 0; i < n; ++i)
+    if (prompt_lens[i] < 1 || max_new[i] < 1 || gen_lens[i] < 1 || gen_lens[i] > max_new[i])
+      return kBad;
+  ServeGeom g;
+  g.max_rows = max_rows; g.num_pages = num_pages; g.pages_per_tile = pages_per_tile;
+  g.page_size = page_size; g.window = 0; g.max_seq_len = max_seq_len;
+  ServePlan plan;
+  plan.begin(g, prefix_cache != 0);
+  {
+    const int32_t* tok = tokens;
+    for (int i = 0; i < n; ++i) {
+      if (plan.submit(prompt_lens[i], max_new[i], tok) != i) return -1;
+      tok += prompt_lens[i];
+    }
+  }
+  long long count = 0;
+  auto rec = [&](long long step, long long kind, long long id, long long row, long long aux,
+                 long long aux2) {
+    if (count < room) {
+      long long* q = out + 6 * count;
+      q[0] = step, q[1] = kind, q[2] = id, q[3] = row, q[4] = aux, q[5] = aux2;
+    }
+    ++count;
+  };
+  int32_t next_page = 0;  // stand-ins for the page ids a hold would report
+  for (long long step = 1; plan.live() + plan.waiting() > 0; ++step) {
+    const int before = plan.live(), na = plan.admit();
+    // (the evictions of a step all precede its publications, so an evicted
+    // block's id names what it named when it was published)
+    for (const ServeEvict& e : plan.evictions()) rec(step, 5, e.block, -1, e.depth, 0);
+    plan.evictions().clear();
+    long long committed = plan.committed();
+    for (int r = before + na - 1; r >= before; --r) committed -= plan.row(r).need;
+    for (int r = before; r < before + na; ++r) {
+      committed += plan.row(r).need;  // (cache off: as serve_plan_sim_tune counts it)
+      rec(step, 0, plan.row(r).id, r, prefix_cache ? plan.row(r).committed_after : committed,
+          plan.row(r).hit_blocks);
+    }
+    if (plan.deferred() >= 0) rec(step, 4, plan.deferred(), -1, 0, 0);
+    if (plan.live() == 0) return kBad;  // (not reached: a lone request always fits)
+    for (int r = before; r < before + na; ++r) {
+      const size_t had = plan.row(r).blocks.size();
+      plan.publish(r, [&](int, int32_t* pages) {
+        for (int i = 0; i < pages_per_tile; ++i) pages[i] = next_page++;
+        return 0;
+      });
+      for (size_t k = had; k < plan.row(r).blocks.size(); ++k)
+        rec(step, 6, plan.row(r).id, r, plan.row(r).blocks[k], (long long)k);
+    }
+    rec(step, 7, -1, -1, plan.committed(), plan.idle_pages());
+    plan.finish_step(
+        [&](int r, const ServeReq& q) {
+          rec(step, 1, q.id, r, q.delivered, 0);
+          return q.delivered + 1 == gen_lens[q.id] && gen_lens[q.id] < q.max_new;
+        },
+        [&](int r, const ServeReq& q, int finish, const ServeMove* mv) {
+          rec(step, 3, q.id, r, finish, 0);
+          if (mv) rec(step, 2, plan.row(mv->dst).id, mv->dst, mv->src, 0);
+          return 0;
+        });
+    rec(step, 8, -1, -1, plan.committed(), plan.idle_pages());
+  }
+  if (stats) {
+    const ServePrefixStats& s = plan.prefix_stats();
+    stats[0] = s.due, stats[1] = s.hit, stats[2] = plan.index().cached_blocks();
+    stats[3] = plan.idle_pages(), stats[4] = s.evicted, stats[5] = s.deferrals;
+  }
+  if (count > 2147483647LL) return kBad;
+  return count > room ? -(int)count : (int)count;
+}
+
 // Tuning hook: the beam search's host bookkeeping (beam_plan.hpp) run on
 // explicit candidates without a device, as llm_decoder_beam_search runs it on
 // the device's: cand_* [steps][num_seqs][2W] in rank order, min(max_new,

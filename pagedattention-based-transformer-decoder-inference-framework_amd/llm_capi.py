@@ -119,6 +119,18 @@ class LlmServeEvent(ctypes.Structure):
                 ("row", ctypes.c_int32), ("finish", ctypes.c_int32)]
 
 
+class LlmServeOptions(ctypes.Structure):
+    """llm_serve_options of llm_decoder_serve_begin_opts."""
+    _fields_ = [("prefix_cache", ctypes.c_int)]
+
+
+class LlmPrefixStats(ctypes.Structure):
+    """llm_prefix_stats of llm_decoder_serve_prefix_stats."""
+    _fields_ = [(n, ctypes.c_longlong) for n in
+                ("positions_due", "positions_hit", "cached_blocks", "idle_pages",
+                 "evicted_blocks", "deferrals")]
+
+
 class LlmError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"[llm status {status}] {msg}")
@@ -207,6 +219,8 @@ _SIGS = {
     # continuous batching (llm_decoder_serve_*)
     "llm_decoder_serve_begin": (c_int, [c_void_p]),
     "llm_decoder_serve_end": (c_int, [c_void_p]),
+    "llm_decoder_serve_begin_opts": (c_int, [c_void_p, ctypes.POINTER(LlmServeOptions)]),
+    "llm_decoder_serve_prefix_stats": (c_int, [c_void_p, ctypes.POINTER(LlmPrefixStats)]),
     "llm_decoder_submit": (c_int, [c_void_p, c_i32p, c_int, ctypes.POINTER(LlmRequestOptions),
                                    ctypes.POINTER(c_ll)]),
     "llm_decoder_submit_logprobs": (c_int, [c_void_p, c_i32p, c_int,
@@ -224,6 +238,10 @@ _SIGS = {
     # tuning library only: the continuous-batching scheduler (csrc/serve_plan.hpp)
     "serve_plan_sim_tune": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_ll, c_int, c_int,
                                     c_int, c_int, ctypes.POINTER(c_ll), c_int]),
+    # tuning library only: ... with prompts and the prefix cache (csrc/prefix_cache.hpp)
+    "serve_prefix_sim_tune": (c_int, [c_i32p, c_i32p, c_i32p, c_i32p, c_int, c_int, c_ll, c_int,
+                                      c_int, c_int, c_int, ctypes.POINTER(c_ll), c_int,
+                                      ctypes.POINTER(c_ll)]),
     # tuning library only: the beam search's host bookkeeping (csrc/beam_plan.hpp)
     "beam_book_tune": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float] +
                        [c_void_p] * 7),
@@ -275,6 +293,9 @@ _SIGS = {
     "kv_cache_reserve": (c_int, [c_void_p, c_int, c_int]),
     "kv_cache_fork": (c_int, [c_void_p, c_int, c_int]),
     "kv_cache_release": (c_int, [c_void_p, c_int]),
+    "kv_cache_hold_tile": (c_int, [c_void_p, c_int, c_int, c_i32p]),
+    "kv_cache_attach_tile": (c_int, [c_void_p, c_int, c_int, c_i32p]),
+    "kv_cache_drop_pages": (c_int, [c_void_p, c_i32p]),
     "kv_cache_release_before": (c_int, [c_void_p, c_int, c_int]),
     "llm_decoder_set_window": (c_int, [c_void_p, c_int]),
     "llm_decoder_window": (c_int, [c_void_p]),
@@ -826,6 +847,55 @@ def serve_plan_sim(prompt_lens, max_new, gen_lens, *, max_rows, num_pages, pages
     got = tune.serve_plan_sim_tune(*args, out, room)
     assert got == room, (got, room)
     return [tuple(out[5 * i:5 * i + 5]) for i in range(room)]
+
+
+SERVE_DEFER, SERVE_EVICT, SERVE_PUBLISH, SERVE_STATE_ADMITTED, SERVE_STATE_END = range(4, 9)
+PREFIX_STATS = ("positions_due", "positions_hit", "cached_blocks", "idle_pages", "evicted_blocks",
+                "deferrals")
+
+
+def serve_prefix_sim(prompts, max_new, gen_lens, *, max_rows, num_pages, pages_per_tile,
+                     page_size, max_seq_len, prefix_cache=True):
+    """serve_prefix_sim_tune (tuning library): serve_plan_sim on prompts (lists
+    of token ids), with the prefix cache or without.  Returns (records, stats):
+    records (step, kind, id, row, aux, aux2) -- see the entry for the kinds --
+    and the PREFIX_STATS counters as a dict; None if a request is refused."""
+    tune = load_tune()
+    n = len(prompts)
+    flat = [t for p in prompts for t in p]
+    arr = ctypes.c_int32 * max(n, 1)
+    args = ((ctypes.c_int32 * max(len(flat), 1))(*flat), arr(*[len(p) for p in prompts]),
+            arr(*max_new), arr(*gen_lens), n, max_rows, num_pages, pages_per_tile, page_size,
+            max_seq_len, int(prefix_cache))
+    count = tune.serve_prefix_sim_tune(*args, None, 0, None)
+    if count == -1:
+        return None
+    if count == -2 ** 31:
+        raise ValueError("serve_prefix_sim: bad arguments")
+    room = abs(count)
+    out = (c_ll * (6 * max(room, 1)))()
+    stats = (c_ll * 6)()
+    got = tune.serve_prefix_sim_tune(*args, out, room, stats)
+    assert got == room, (got, room)
+    return ([tuple(out[6 * i:6 * i + 6]) for i in range(room)], dict(zip(PREFIX_STATS, stats)))
+
+
+def kv_hold_tile(cache, beam, tile, n_pages):
+    """kv_cache_hold_tile: the tile's n_pages = L * H page ids, one more
+    reference taken on each."""
+    pages = (ctypes.c_int32 * n_pages)()
+    check(load().kv_cache_hold_tile(cache, beam, tile, pages))
+    return list(pages)
+
+
+def kv_attach_tile(cache, beam, tile, pages):
+    """kv_cache_attach_tile: map held pages into an unmapped tile of `beam`."""
+    check(load().kv_cache_attach_tile(cache, beam, tile, (ctypes.c_int32 * len(pages))(*pages)))
+
+
+def kv_drop_pages(cache, pages):
+    """kv_cache_drop_pages: give back the references of a hold."""
+    check(load().kv_cache_drop_pages(cache, (ctypes.c_int32 * len(pages))(*pages)))
 
 
 def beam_book(cand_score, cand_parent, cand_token, W, V, max_new, eos_token, length_penalty):
