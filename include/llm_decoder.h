@@ -174,6 +174,34 @@ int pa_decode_window(const pa_kv_view* kv, const float* q, float* out, const int
 int pa_decode_window_plan(const pa_kv_view* kv, int B, int H, int D, int T, int pages_per_split,
                           int window, int* nsplit, int* form);
 
+/* pa_decode for rows that share leading pages (prefix caching): a GROUP is
+ * G >= 2 batch rows, any rows in any order, whose page-table entries are equal,
+ * per head, on their first P tiles.  Group j's rows are
+ * group_rows[group_off[j] .. group_off[j+1]) and its P is group_tiles[j]
+ * (host arrays; group_off has ngroups + 1 entries from 0).  The groups' shared
+ * tiles are read once per group by an MFMA kernel (the arithmetic of
+ * pa_prefill, within 1e-3 relative of pa_decode), every row's other tiles by
+ * pa_decode's split kernel from tile P on, and one merge joins them; rows in
+ * no group run as in pa_decode.  Rows are taken in place (row b reads
+ * page-table row b; no beam_ids), out is fp32 [B][H][D].  fp16 or LLM_FP8
+ * pools, head_dim 64 or 128, page_size 16 or 32 (else LLM_ERR_UNSUPPORTED).
+ * LLM_ERR_INVALID, before any launch: a row in two groups or outside the
+ * batch, a group of fewer than 2 rows, members whose pages differ on a claimed
+ * tile, a claimed tile at or past a member's context (P * page_size must be
+ * <= context_lens[b], or T), a workspace smaller than
+ * pa_decode_shared_workspace_bytes(kv, B, T).  A pa_kv_view has no host mirror
+ * of its table, so the entry waits for the stream and reads the members'
+ * claimed entries and the contexts back to check them: it is a standalone
+ * entry, not one to capture into a graph.  (The decoder's own grouped steps,
+ * llm_decoder_set_shared_attention, take their groups from its prefix index
+ * and check nothing on the device.) */
+size_t pa_decode_shared_workspace_bytes(const pa_kv_view* kv, int B, int T);
+int pa_decode_shared(const pa_kv_view* kv, const float* q, float* out,
+                     const int32_t* context_lens, int B, int H, int D, int T, float sm_scale,
+                     const int32_t* group_rows, const int32_t* group_off,
+                     const int32_t* group_tiles, int ngroups, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Causal paged attention of a prompt chunk: the reference's prefill pass
  * (AttentionCUDA's is_prefill flag, attention/attention_cuda.hpp:21; maths of
  * cpu_paged_attention_forward, attention_cpu/cpu_attention_kernel.cpp:37-129,
@@ -920,6 +948,33 @@ typedef struct llm_prefix_stats {
   long long deferrals;       /* admissions ended by the same-step rule */
 } llm_prefix_stats;
 int llm_decoder_serve_prefix_stats(const llm_decoder* d, llm_prefix_stats* out);
+/* Shared-prefix decode attention (off by default).  min_pages > 0: in serving
+ * sessions with a prefix cache, live rows whose prompts hit or published the
+ * same blocks are grouped when they share at least min_pages leading tiles
+ * (pages per head), and a step with a group runs its attention as a
+ * shared-prefix launch: the group's shared pages are read once per group by an
+ * MFMA kernel, the rows' other pages by the split kernel, one merge joins them
+ * (pa_decode_shared's launch).  Such a step runs the split + merge forms only
+ * (no workgroup merge, no fused o_proj), so its logits differ from an unshared
+ * step's by fp32 rounding.  The groups are planned again whenever the live rows
+ * change; one level of sharing, a row in at most one group.  min_pages 0: off;
+ * LLM_SHARED_DEFAULT_MIN_PAGES is the value for "on" without a number.  Set
+ * while no rows are active and not serving, else LLM_ERR_INVALID; min_pages
+ * < 0 LLM_ERR_INVALID; LLM_ERR_UNSUPPORTED with a sliding window set (either
+ * order), and for pools the group kernel does not take (fp16 or FP8 pages,
+ * head_dim 64 or 128, page_size 16 or 32).  Entries other than serving share
+ * nothing and are unaffected. */
+#define LLM_SHARED_DEFAULT_MIN_PAGES 16
+int llm_decoder_set_shared_attention(llm_decoder* d, int min_pages);
+int llm_decoder_shared_attention(const llm_decoder* d);
+/* Counters of the current serving session (zeros with sharing off). */
+typedef struct llm_shared_stats {
+  long long shared_steps;       /* decode steps that ran a shared-prefix launch */
+  long long grouped_row_steps;  /* rows in a group, summed over those steps */
+  long long page_reads_saved;   /* sum over those steps and groups of (G - 1) * P *
+                                 * num_layers * num_heads: pages the rows did not re-read */
+} llm_shared_stats;
+int llm_decoder_shared_stats(const llm_decoder* d, llm_shared_stats* out);
 /* Leave serving mode: every request, waiting or live, is dropped without an
  * event, the cache is cleared (a prefix cache's blocks with it) and no rows
  * stay active (batch 0).

@@ -594,6 +594,22 @@ class Decoder {
   // positions (0: off), before any rows are active
   void set_window(int window) { check(llm_decoder_set_window(d_, window)); }
   int window() const { return llm_decoder_window(d_); }
+  // llm_decoder_set_shared_attention: serving rows that share >= min_pages
+  // leading pages read them once per group (0: off; < 0: the default length)
+  void set_shared_attention(int min_pages) {
+    check(llm_decoder_set_shared_attention(
+        d_, min_pages < 0 ? LLM_SHARED_DEFAULT_MIN_PAGES : min_pages));
+  }
+  int shared_attention() const { return llm_decoder_shared_attention(d_); }
+  // {shared_steps, grouped_row_steps, page_reads_saved} of the serving session
+  py::dict shared_stats() const {
+    llm_shared_stats p{};
+    check(llm_decoder_shared_stats(d_, &p));
+    py::dict s;
+    s["shared_steps"] = p.shared_steps; s["grouped_row_steps"] = p.grouped_row_steps;
+    s["page_reads_saved"] = p.page_reads_saved;
+    return s;
+  }
   std::string kv_dtype() const {
     return llm_decoder_kv_dtype(d_) == LLM_FP8 ? "float8_e4m3fn" : "float16";
   }
@@ -868,6 +884,9 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def_property_readonly("rope", &Decoder::rope)
         .def("set_window", &Decoder::set_window, py::arg("window"))
         .def_property_readonly("window", &Decoder::window)
+        .def("set_shared_attention", &Decoder::set_shared_attention, py::arg("min_pages") = -1)
+        .def_property_readonly("shared_attention", &Decoder::shared_attention)
+        .def("shared_stats", &Decoder::shared_stats)
         .def_property_readonly("kv_dtype", &Decoder::kv_dtype)
         .def_property_readonly("prefill_kernel", &Decoder::prefill_kernel)
         .def_property_readonly("kv_handle", &Decoder::kv_handle);

@@ -201,12 +201,50 @@ extern "C" int llm_decoder_set_window(llm_decoder* d, int window) {
   LLM_REQUIRE(d->batch == 0, "llm_decoder_set_window: rows are active (set the window before "
                              "begin_* / generate / prefill)");
   LLM_REQUIRE(window >= 0, "llm_decoder_set_window: window must be >= 0 (0: off)");
+  if (window > 0 && d->share_min > 0)
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_set_window: shared-prefix attention is on "
+                                     "(llm_decoder_set_shared_attention): it takes no window");
   d->window = window;
   d->drop_step_graph();  // the step graph carries the window as a kernel argument
   return LLM_OK;
 }
 
 extern "C" int llm_decoder_window(const llm_decoder* d) { return d ? d->window : -1; }
+
+extern "C" int llm_decoder_set_shared_attention(llm_decoder* d, int min_pages) {
+  LLM_REQUIRE(d, "llm_decoder_set_shared_attention: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  NOT_SERVING(d, "llm_decoder_set_shared_attention");
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_shared_attention: rows are active (set it before "
+                             "any row starts)");
+  LLM_REQUIRE(min_pages >= 0, "llm_decoder_set_shared_attention: min_pages must be >= 0 (0: off)");
+  if (min_pages > 0) {
+    if (d->window > 0)
+      return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_set_shared_attention: the decoder has a "
+                                       "sliding window (shared-prefix launches take none)");
+    pa_kv_view view;
+    RET_IF(kv_cache_view(d->kv, 0, &view));
+    if (!pa_shared_supported(&view))
+      return fail(LLM_ERR_UNSUPPORTED,
+                  "llm_decoder_set_shared_attention: fp16 or FP8 pages with head_dim 64 or 128 "
+                  "and page_size 16 or 32 only");
+    // the tables, and partials with the prefix slots beside the suffix splits
+    if (!d->sh_meta.p) RET_IF(d->sh_meta.alloc(share_tables_cap(d->maxB)));
+    const size_t need = pa_decode_shared_workspace_bytes(&view, d->maxB, d->cfg.max_seq_len);
+    if (need > d->attn_ws_bytes) {
+      LLM_HIP_RET(hipStreamSynchronize(d->stream));
+      RET_IF(d->attn_ws.alloc(need));
+      d->attn_ws_bytes = need;
+    }
+  }
+  d->share_min = min_pages;
+  d->drop_step_graph();
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_shared_attention(const llm_decoder* d) {
+  return d ? d->share_min : -1;
+}
 
 extern "C" void llm_decoder_destroy(llm_decoder* d) {
   if (!d) return;

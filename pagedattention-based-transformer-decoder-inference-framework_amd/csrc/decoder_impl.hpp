@@ -16,6 +16,7 @@
 #include "pa_decode.hpp"
 #include "row_ops.hpp"
 #include "serve_plan.hpp"
+#include "share_plan.hpp"
 
 using namespace llm;
 
@@ -84,6 +85,10 @@ struct Rows {
   bool is_prefill() const { return prefill_row >= 0 || prefill_ntile > 0; }
   uint8_t* attn_ws = nullptr;
   size_t attn_ws_bytes = 0;
+  // decode rows of a serving step with shared-prefix groups (else NULL): the
+  // attention is a shared-prefix launch (pa_decode_internal's `shared`), which
+  // keeps to the split + merge forms -- no fused o_proj, no workgroup merge
+  const PaShared* shared = nullptr;
   // FP16 decode rows: the o_proj runs inside the attention's workgroup merge
   // (oproj_fusable) through these int64 columns and writes oproj_out (x, or a
   // scratch row for llm_decoder_run_attention); no o_proj launch
@@ -297,6 +302,22 @@ struct llm_decoder {
   std::vector<int32_t> hs_topk, hs_pos, hs_ctx, hs_tok, hs_next;
   std::vector<uint64_t> hs_seed;
   bool serve_dirty = false;
+  // Shared-prefix attention (llm_decoder_set_shared_attention; share_min 0:
+  // off).  serve_upload plans the live rows' groups (share_plan.hpp) from their
+  // block chains whenever the rows changed and uploads the tables into
+  // sh_meta ([share_tables_cap(max_batch)] int32, fixed addresses: a captured
+  // step replays with new table contents); share is the launch those tables
+  // drive (ntile 0: this step shares nothing and runs as without the feature).
+  // Its geometry is part of the step graph's identity: serve_upload drops the
+  // graph when it changes.  sh_rows / sh_saved: the current plan's grouped rows
+  // and (G - 1) * P sum, added to the session's counters by every step.
+  int share_min = 0;
+  DevBuf<int32_t> sh_meta;
+  std::vector<int32_t> hs_meta;
+  PaShared share;
+  long long sh_rows = 0, sh_saved = 0;
+  llm_shared_stats share_stats{};
+  int share_replan();
   long long graph_instantiations = 0;  // by serving steps (llm_decoder_serve_stats)
   int serve_upload();
   int serve_release(int row, long long id, const ServeMove* mv);

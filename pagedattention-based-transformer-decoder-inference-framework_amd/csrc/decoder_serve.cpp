@@ -34,7 +34,46 @@ int llm_decoder::serve_upload() {
   LLM_HIP_RET(up(sv_seed.p, hs_seed.data(), sizeof(uint64_t)));
   LLM_HIP_RET(up(pos.p, hs_pos.data(), sizeof(int32_t)));
   LLM_HIP_RET(up(ctx.p, hs_ctx.data(), sizeof(int32_t)));
+  if (share_min > 0) RET_IF(share_replan());
   serve_dirty = false;
+  return LLM_OK;
+}
+
+// The live rows' shared-prefix groups (share_plan.hpp), from the chains of
+// blocks they hit or published, and their device tables.  A changed launch
+// geometry changes the step graph (grid, partial layout, forms); the same
+// geometry replays the captured step over the new table contents.
+int llm_decoder::share_replan() {
+  const int n = plan.live();
+  std::vector<ShareRow> rows(n);
+  for (int r = 0; r < n; ++r) {
+    const std::vector<int>& b = plan.row(r).blocks;
+    rows[r] = ShareRow{b.data(), (int)b.size(), h_pos[r]};
+  }
+  const std::vector<ShareGroup> groups = share_plan(rows, TS, share_min);
+  const ShareTables tb = share_tables(groups, n);
+  const ShareLaunch sl = share_launch(tb.ntile, H, tb.max_tiles, TS);
+  sh_rows = sh_saved = 0;
+  for (const ShareGroup& g : groups) {
+    sh_rows += (long long)g.rows.size();
+    sh_saved += share_saving(g) * L * H;
+  }
+  PaShared next;
+  if (sl.ntile > 0) {
+    hs_meta = tb.image;  // (staging: untouched until the step's closing synchronisation)
+    LLM_HIP_RET(hipMemcpyAsync(sh_meta.p, hs_meta.data(), sizeof(int32_t) * hs_meta.size(),
+                               hipMemcpyHostToDevice, stream));
+    next.tiles = sh_meta.p;
+    next.rows = sh_meta.p + tb.rows_off;
+    next.first_tile = sh_meta.p + tb.first_off;
+    next.ntile = sl.ntile, next.npre = sl.npre, next.bps = sl.bps;
+  }
+  // (rows_off / first_off follow ntile and the grouped row count: kernel
+  // arguments of the captured step, compared with the geometry)
+  if (next.ntile != share.ntile || next.npre != share.npre || next.bps != share.bps ||
+      next.rows != share.rows || next.first_tile != share.first_tile)
+    drop_step_graph();
+  share = next;
   return LLM_OK;
 }
 
@@ -55,6 +94,7 @@ int llm_decoder::serve_release(int row, long long id, const ServeMove* mv) {
     h_pos[mv->src] = 0;
     serve_dirty = true;
   }
+  if (share_min > 0) serve_dirty = true;  // a group may have lost a member: plan again
   batch = plan.live();
   return LLM_OK;
 }
@@ -113,6 +153,11 @@ int llm_decoder::serve_step(float* logits_dev, llm_serve_event* events, int* n_e
   const int rc = run_step(hs_tok.data(), logits_dev, hs_next.data(), stream);
   if (rc != LLM_ERR_RANGE) RET_IF(rc);  // (a clamped step still produced its ids)
   graph_instantiations += new_graph;
+  if (share.ntile > 0) {
+    share_stats.shared_steps += 1;
+    share_stats.grouped_row_steps += sh_rows;
+    share_stats.page_reads_saved += sh_saved;
+  }
   *n_events = live;
   RET_IF(plan.finish_step(
       [&](int r, const ServeReq& q) {
@@ -182,6 +227,9 @@ static int serve_begin(llm_decoder* d, bool prefix_cache) {
   geom.window = d->window;
   geom.max_seq_len = d->cfg.max_seq_len;
   d->plan.begin(geom, prefix_cache);
+  d->share = PaShared{};
+  d->share_stats = llm_shared_stats{};
+  d->sh_rows = d->sh_saved = 0;
   d->requests.clear();
   d->serve_dirty = false;
   d->serving = true;
@@ -214,6 +262,13 @@ extern "C" int llm_decoder_serve_prefix_stats(const llm_decoder* d, llm_prefix_s
   return LLM_OK;
 }
 
+extern "C" int llm_decoder_shared_stats(const llm_decoder* d, llm_shared_stats* out) {
+  LLM_REQUIRE(d && out, "llm_decoder_shared_stats: NULL");
+  std::lock_guard<std::mutex> g(const_cast<llm_decoder*>(d)->mu);
+  *out = d->share_stats;
+  return LLM_OK;
+}
+
 extern "C" int llm_decoder_serve_end(llm_decoder* d) {
   LLM_REQUIRE(d, "llm_decoder_serve_end: NULL");
   std::lock_guard<std::mutex> g(d->mu);
@@ -222,6 +277,7 @@ extern "C" int llm_decoder_serve_end(llm_decoder* d) {
   d->plan.begin(d->plan.geom());
   d->requests.clear();
   d->serving = false;
+  d->share = PaShared{};
   d->step_logprobs = false;
   d->hl_n = 0;
   d->drop_step_graph();

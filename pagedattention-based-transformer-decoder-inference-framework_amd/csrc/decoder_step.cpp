@@ -101,7 +101,7 @@ bool llm_decoder::quant_prologue(const Rows& R) const {
 // heads; otherwise the o_proj GEMM runs as before.
 bool llm_decoder::oproj_fusable(const Rows& R) {
   if (wdtype != LLM_F16 || kvt != LLM_F16 || R.is_prefill() || R.row_group != 1 ||
-      R.beam_rows || !wo_heads.p ||
+      R.beam_rows || R.shared || !wo_heads.p ||
       D > 128 || H > 64 || !oproj_fuse_on())
     return false;
   Rows r = R;
@@ -119,7 +119,7 @@ bool llm_decoder::oproj_fusable(const Rows& R) {
 // o_proj input -- in place of split + pa_merge_row_kernel (C5: 5 splits of
 // 103 pages -> 8 of 65 merged in the workgroup).
 bool llm_decoder::wgm_quant_ok(const Rows& R) {
-  if (wdtype != LLM_I8 || R.is_prefill() || R.row_group != 1 || R.beam_rows ||
+  if (wdtype != LLM_I8 || R.is_prefill() || R.row_group != 1 || R.beam_rows || R.shared ||
       quant_prologue(R))
     return false;
   Rows r = R;
@@ -160,6 +160,7 @@ int llm_decoder::attn_request(const Rows& R, pa_kv_view* view, PaRequest* rq, in
   rq->rows16 = out == PaOut::OPROJ && tap_q;  // the taps read the packed o_proj input
   rq->steal_ctr = R.row_group >= 4 && beam_steal_on();
   rq->window = window;
+  rq->shared_pre = R.shared ? R.shared->npre : 0;
   return LLM_OK;
 }
 
@@ -203,7 +204,7 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
                                R.attn_ws, R.attn_ws_bytes, st, &ro, window);
   }
   RET_IF(pa_decode_internal(&view, rq, R.q, hid, R.o, R.beam_rows, R.ctx, sm, R.attn_ws,
-                            R.attn_ws_bytes, st, &ro));
+                            R.attn_ws_bytes, st, &ro, nullptr, R.shared));
   if (R.wgm_quant)  // the packed int8 o_proj input + row scales
     LLM_HIP_RET(launch_quantize_rows(R.o, R.n, hid, static_cast<int8_t*>(R.act), R.sa, st, 1));
   return LLM_OK;
@@ -282,6 +283,7 @@ int llm_decoder::decode_rows(Rows* out, bool scratch_oproj) {
   R.row_group = row_group;
   R.attn_ws = attn_ws.p;
   R.attn_ws_bytes = attn_ws_bytes;
+  if (serving && share.ntile > 0) R.shared = &share;
   if (oproj_fusable(R)) {
     if (scratch_oproj && !oacc_run.p) {
       RET_IF(oacc_run.alloc(oacc.n));

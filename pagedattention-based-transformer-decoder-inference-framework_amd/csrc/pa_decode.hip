@@ -28,7 +28,31 @@ struct PaMergeRowArgs {
   int ctx_p0;  // >= 0 and context_lens NULL: row b's context is ctx_p0 + b + 1 (prefill)
   float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
   int window;  // the split launch's (PaSplitArgs::window): splits relative to the row's window
+  // shared-prefix launches (PaSplitArgs::first_tile / npre; NULL / 0: off)
+  const int32_t* first_tile;
+  int npre;
 };
+
+// The partial slots of row b in a merge: a (row, head) holds npre prefix slots
+// (the group kernel's, live only for a row with first_tile > 0) and then
+// nsplit suffix slots, of which the row's own count from its first live tile
+// hold a partial.  The merge of a grouped row reads the npre + ns slots from
+// the front; that of any other row skips the prefix slots, which nothing wrote.
+// Without first_tile: skip 0 and ns as before.
+struct MergeSlots {
+  int skip, nsplit, ns;
+};
+__device__ __forceinline__ MergeSlots merge_slots(const int32_t* first_tile, int npre, int b,
+                                                  int Tb, int ntiles, int window, int TS, int pps,
+                                                  int nsplit) {
+  PaSpan span = row_span(Tb, ntiles, window, TS);
+  const int ft = first_tile ? first_tile[b] : 0;
+  if (first_tile) span = row_first(span, ft, ntiles, TS);
+  // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
+  const int ns = pps < 0 ? nsplit : row_nsplits(pps, nsplit, span.n_live);
+  const int pre = ft > 0 ? npre : 0;
+  return {npre - pre, nsplit + pre, ns + pre};
+}
 
 // One head's split merge (flash-decoding LSE combine) by one wave, DPL =
 // output dims per lane (D / 64, at least 1).  The head's split weights (m, l),
@@ -119,6 +143,8 @@ struct PaMergeArgs {
   int B, H, D, T, TS, pps, nsplit, max_tiles;
   float out_scale;  // multiplies every merged head (LLM_FP8 pools: the V scale; else 1)
   int window;  // the split launch's (PaSplitArgs::window): splits relative to the row's window
+  const int32_t* first_tile;  // shared-prefix launches (PaMergeRowArgs)
+  int npre;
 };
 
 template <int DPL>
@@ -130,13 +156,12 @@ __global__ __launch_bounds__(256) void pa_merge_kernel(PaMergeArgs a) {
   int Tb = a.context_lens ? a.context_lens[b] : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + a.TS - 1) / a.TS, a.max_tiles);
-  // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
-  const int ns = a.pps < 0 ? a.nsplit
-                           : row_nsplits(a.pps, a.nsplit, row_span(Tb, ntiles, a.window, a.TS).n_live);
+  const MergeSlots ms = merge_slots(a.first_tile, a.npre, b, Tb, ntiles, a.window, a.TS, a.pps,
+                                    a.nsplit);
+  const size_t slot = (size_t)bh * (a.nsplit + a.npre) + ms.skip;
   float acc[DPL];
-  const float inv = a.out_scale * merge_head<DPL, 16>(a.part_ml + (size_t)bh * a.nsplit * 2,
-                                                      a.part_acc + (size_t)bh * a.nsplit * a.D,
-                                                      a.nsplit, ns, a.D, acc);
+  const float inv = a.out_scale * merge_head<DPL, 16>(a.part_ml + slot * 2, a.part_acc + slot * a.D,
+                                                      ms.nsplit, ms.ns, a.D, acc);
   float* o = a.out + (size_t)bh * a.D;
 #pragma unroll
   for (int j = 0; j < DPL; ++j) {
@@ -160,15 +185,14 @@ __global__ __launch_bounds__(1024) void pa_merge_row_kernel(PaMergeRowArgs a) {
   int Tb = a.context_lens ? a.context_lens[b] : a.ctx_p0 >= 0 ? a.ctx_p0 + b + 1 : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + a.TS - 1) / a.TS, a.max_tiles);
-  // pps < 0: every split holds a partial (beam launches: cost-balanced splits)
-  const int ns = a.pps < 0 ? a.nsplit
-                           : row_nsplits(a.pps, a.nsplit, row_span(Tb, ntiles, a.window, a.TS).n_live);
+  const MergeSlots ms = merge_slots(a.first_tile, a.npre, b, Tb, ntiles, a.window, a.TS, a.pps,
+                                    a.nsplit);
   for (int h = w; h < a.H; h += nw) {
-    const size_t bh = (size_t)b * a.H + h;
+    const size_t slot = ((size_t)b * a.H + h) * (a.nsplit + a.npre) + ms.skip;
     float acc[DPL];
-    const float inv = a.out_scale * merge_head<DPL, kMergeBatch>(a.part_ml + bh * a.nsplit * 2,
-                                                                 a.part_acc + bh * a.nsplit * a.D,
-                                                                 a.nsplit, ns, a.D, acc);
+    const float inv = a.out_scale * merge_head<DPL, kMergeBatch>(a.part_ml + slot * 2,
+                                                                 a.part_acc + slot * a.D,
+                                                                 ms.nsplit, ms.ns, a.D, acc);
     float* dst = row + h * a.D;
 #pragma unroll
     for (int j = 0; j < DPL; ++j) {
@@ -377,9 +401,10 @@ extern "C" size_t pa_decode_workspace_bytes(int B, int H, int D, int max_tiles,
 int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                                   const int32_t* context_lens, int B, int H, int D, int T, int TS,
                                   int pps, int nsplit, int max_tiles, hipStream_t st,
-                                  float out_scale, int window) {
+                                  float out_scale, int window, const int32_t* first_tile,
+                                  int npre) {
   PaMergeArgs mg{part_acc, part_ml, out, context_lens, B, H, D, T, TS, pps, nsplit, max_tiles,
-                 out_scale, window};
+                 out_scale, window, first_tile, npre};
   const dim3 grid((B * H + 3) / 4);
   if (D <= 64)
     hipLaunchKernelGGL(pa_merge_kernel<1>, grid, dim3(256), 0, st, mg);
@@ -394,11 +419,13 @@ int llm::pa_merge_splits_internal(const float* part_acc, const float* part_ml, f
 int llm::pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                                 const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                                 int B, int H, int D, int T, int TS, int pps, int nsplit,
-                                int max_tiles, hipStream_t st, float out_scale, int window) {
+                                int max_tiles, hipStream_t st, float out_scale, int window,
+                                const int32_t* first_tile, int npre) {
   PaMergeRowArgs mg{part_acc, part_ml, out, rows ? rows->q : nullptr,
                     rows ? rows->inv_scale : nullptr,
                     rows ? static_cast<_Float16*>(rows->out16) : nullptr, context_lens, B, H, D, T,
-                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0, out_scale, window};
+                    TS, pps, nsplit, max_tiles, rows ? rows->pack : 0, ctx_p0, out_scale, window,
+                    first_tile, npre};
   const int threads = 64 * std::min(16, H);  // one wave per head (heads > 16 loop)
   const size_t lds = (size_t)H * D * sizeof(float);
   if (D <= 64)
@@ -414,7 +441,8 @@ int llm::pa_merge_rows_internal(const float* part_acc, const float* part_ml, flo
 int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const float* q, int q_stride,
                             float* out, const int32_t* beam_ids, const int32_t* context_lens,
                             float sm_scale, void* workspace, size_t workspace_bytes,
-                            hipStream_t st, const PaRowOutputs* rows, PaLaunch* plan) {
+                            hipStream_t st, const PaRowOutputs* rows, PaLaunch* plan,
+                            const PaShared* shared) {
   const int B = rq.B, H = rq.H, D = rq.D, T = rq.T;
   LLM_REQUIRE(kv != nullptr, "pa_decode: kv view is NULL");
   LLM_REQUIRE(B >= 0 && H > 0 && D > 0 && T >= 0, "pa_decode: bad B/H/D/T");
@@ -422,6 +450,14 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
   if (rq.window > 0 && rq.row_group > 1)
     return fail(LLM_ERR_UNSUPPORTED, "pa_decode: a sliding window needs ungrouped rows "
                                      "(row_group 1)");
+  if (rq.shared_pre > 0 && (rq.window > 0 || rq.row_group > 1))
+    return fail(LLM_ERR_UNSUPPORTED, "pa_decode: a shared-prefix launch takes no sliding window "
+                                     "and no row groups");
+  LLM_REQUIRE(plan || (rq.shared_pre > 0) == (shared != nullptr),
+              "pa_decode: shared-prefix tables and the request's shared_pre go together");
+  LLM_REQUIRE(!shared || (shared->npre == rq.shared_pre && !beam_ids),
+              "pa_decode: a shared-prefix launch takes rows in place (no beam_ids) and the "
+              "tables' own split count");
   if (plan) *plan = PaLaunch{};
   if (B == 0) return LLM_OK;
   // the FP16 decoder's fused o_proj (PaRowOutputs::o_acc): workgroup-merge launches only
@@ -489,7 +525,14 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
     LLM_REQUIRE(workspace != nullptr && workspace_bytes >= p.workspace_bytes,
                 "pa_decode: workspace too small (see pa_decode_workspace_bytes)");
     a.part_acc = static_cast<float*>(workspace);
-    a.part_ml = a.part_acc + (size_t)B * H * p.nsplit * D;
+    a.part_ml = a.part_acc + (size_t)B * H * (p.nsplit + rq.shared_pre) * D;
+  }
+  if (shared) {  // the groups' prefix partials first (disjoint slots: any order would do)
+    a.first_tile = shared->first_tile;
+    a.npre = shared->npre;
+    const int rc = pa_shared_prefix_launch(kv, q, q_stride, a.qscale, *shared, a.part_acc,
+                                           a.part_ml, p.nsplit + shared->npre, st);
+    if (rc != LLM_OK) return rc;
   }
   const PaTuning tn = pa_tuning();
   a.balance16 = tn.beam_balance16;
@@ -522,11 +565,11 @@ int llm::pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const flo
   if (row_out && !p.direct)
     return pa_merge_rows_internal(a.part_acc, a.part_ml, rows->keep_out ? out : nullptr, rows,
                                   context_lens, -1, B, H, D, T, TS, p.beam ? -1 : p.pps, p.nsplit,
-                                  kv->max_tiles, st, out_scale, rq.window);
+                                  kv->max_tiles, st, out_scale, rq.window, a.first_tile, a.npre);
   if (!p.direct) {
     const int r = pa_merge_splits_internal(a.part_acc, a.part_ml, out, context_lens, B, H, D, T,
                                            TS, p.beam ? -1 : p.pps, p.nsplit, kv->max_tiles, st,
-                                           out_scale, rq.window);
+                                           out_scale, rq.window, a.first_tile, a.npre);
     if (r != LLM_OK) return r;
   }
   if (row_out) {  // single split: out is final; convert it in a row pass

@@ -50,6 +50,15 @@ constexpr int kv_elem_size(int kvt) {
                                            : 0;
 }
 
+// The device tables of a shared-prefix launch (share_plan.hpp share_tables)
+// and its key split (share_launch): what pa_shared.hip's group kernel reads.
+struct PaShared {
+  const int32_t* tiles = nullptr;       // [ntile][4] {first index into rows, queries, P, 0}
+  const int32_t* rows = nullptr;        // member batch rows, group after group
+  const int32_t* first_tile = nullptr;  // [B]: P of a grouped row, 0 of any other
+  int ntile = 0, npre = 0, bps = 0;
+};
+
 // The request (pa_plan.hpp) of a launch over a view's pages.
 inline PaRequest pa_request(const pa_kv_view* kv, int B, int H, int D, int T, int pages_per_split,
                             int row_group = 1, PaOut out = PaOut::F32, int window = 0) {
@@ -79,7 +88,21 @@ int pa_plan_device(const PaRequest& rq, PaLaunch* launch, long long resident = -
 int pa_decode_internal(const pa_kv_view* kv, const PaRequest& rq, const float* q, int q_stride,
                        float* out, const int32_t* beam_ids, const int32_t* context_lens,
                        float sm_scale, void* workspace, size_t workspace_bytes, hipStream_t st,
-                       const PaRowOutputs* rows = nullptr, PaLaunch* plan = nullptr);
+                       const PaRowOutputs* rows = nullptr, PaLaunch* plan = nullptr,
+                       const PaShared* shared = nullptr);
+// shared != NULL (with rq.shared_pre = shared->npre): a shared-prefix launch.
+// The group kernel (pa_shared.hip) writes, for every grouped row and head, the
+// softmax state over the row's first first_tile[b] tiles into shared->npre
+// partial slots; the split kernel covers the rest of each row (all of an
+// ungrouped row) and the merge joins both.  Rows are taken in place (no
+// beam_ids).  The caller guarantees what the tables claim: disjoint groups,
+// equal page-table entries of a group's members on its P tiles, P * page_size
+// below every member's context (pa_decode_shared checks it; the decoder's
+// tables come from share_plan).
+bool pa_shared_supported(const pa_kv_view* kv);
+int pa_shared_prefix_launch(const pa_kv_view* kv, const float* q, int q_stride, float qscale,
+                            const PaShared& sh, float* part_acc, float* part_ml, int nslots,
+                            hipStream_t st);
 int pa_pages_per_split(int B, int H, int T, int TS, int max_tiles);
 // Whether the FP16 decoder fuses its o_proj into the attention's workgroup
 // merge (PaRowOutputs::o_acc); always in the product build.
@@ -99,12 +122,14 @@ bool beam_steal_on();
 int pa_merge_rows_internal(const float* part_acc, const float* part_ml, float* out,
                            const PaRowOutputs* rows, const int32_t* context_lens, int ctx_p0,
                            int B, int H, int D, int T, int TS, int pps, int nsplit, int max_tiles,
-                           hipStream_t st, float out_scale = 1.f, int window = 0);
+                           hipStream_t st, float out_scale = 1.f, int window = 0,
+                           const int32_t* first_tile = nullptr, int npre = 0);
 
 int pa_merge_splits_internal(const float* part_acc, const float* part_ml, float* out,
                              const int32_t* context_lens, int B, int H, int D, int T, int TS,
                              int pps, int nsplit, int max_tiles, hipStream_t st,
-                             float out_scale = 1.f, int window = 0);
+                             float out_scale = 1.f, int window = 0,
+                             const int32_t* first_tile = nullptr, int npre = 0);
 
 // Causal MFMA attention of a prompt chunk (csrc/pa_prefill.hip, C entry
 // pa_prefill): out rows i < m = attention of query i (position p0 + i) over

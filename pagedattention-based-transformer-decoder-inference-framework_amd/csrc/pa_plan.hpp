@@ -55,6 +55,11 @@ struct PaRequest {
   // sliding window: row b attends to its last `window` tokens only (0: off, the
   // whole context); ungrouped rows only
   int window = 0;
+  // shared-prefix launch (pa_shared.hip; 0: off): the group kernel writes this
+  // many prefix partial slots per (row, head) in front of the suffix splits,
+  // so partials must exist: split + merge forms only -- no direct form, no
+  // workgroup merge and with it no fused o_proj -- and ungrouped rows, no window
+  int shared_pre = 0;
 };
 
 struct PaLaunch {
@@ -129,8 +134,9 @@ inline int choose_nsplit(int B, int H, int ntiles, int pps_fixed, long long resi
 // chip's resident waves of the plain split kernel, of the beam form (0 where
 // the plain schedule runs instead) and of the tuning build's pa_beam4_kernel;
 // read only for dynamic splits (pps_fixed 0).  LLM_ERR_UNSUPPORTED: the row
-// needs more than kMaxSplits splits of kMaxPps pages, or a window is asked
-// for grouped rows.
+// needs more than kMaxSplits splits of kMaxPps pages (prefix slots of a shared
+// launch included), or a window is asked for grouped rows or a shared launch,
+// or a shared launch for grouped rows.
 inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
                    long long beam_resident, long long beam4_resident, PaLaunch* out) {
   const int B = rq.B, H = rq.H, D = rq.D, TS = rq.TS, row_group = rq.row_group, kvt = rq.kv_dtype;
@@ -143,6 +149,8 @@ inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
   if (rq.window > 0) ntiles_max = std::min(ntiles_max, (rq.window - 1) / TS + 2);
   *out = PaLaunch{};
   if (rq.window > 0 && row_group > 1) return LLM_ERR_UNSUPPORTED;
+  const bool shared = rq.shared_pre > 0;
+  if (shared && (rq.window > 0 || row_group > 1)) return LLM_ERR_UNSUPPORTED;
   const int pps_fixed = rq.pps_fixed > 0 ? std::min(rq.pps_fixed, kMaxPps) : 0;
   // the beam-group form: fp16 pages of two register stages
   const bool beam_shape = kvt == LLM_F16 && split_stages(D, TS, 2) == 2;
@@ -177,7 +185,7 @@ inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
   const bool wgm_kvt = kvt == LLM_F16 ||
                        (kvt == LLM_FP8 && !oproj && !out16 && fp8_wgm_shape_ok(D, TS));
   const bool wgm_ok = (out16 || oproj || f32_rows) && row_group == 1 && wgm_kvt && tn.wg_merge &&
-                      !half_round;
+                      !half_round && !shared;
   if (wgm_ok && pps_fixed <= 0 && !f32_rows) {
     const int nw = choose_nsplit(B, H, ntiles_max, 0, resident_launch, kWgmShortPps);
     if (nw >= 2 && nw <= kWgmMaxSplits) nsplit = nw;
@@ -216,11 +224,12 @@ inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
   }
   if (nsplit > kMaxSplits || (long long)nsplit * (pps_fixed > 0 ? pps_fixed : kMaxPps) < ntiles_max)
     return LLM_ERR_UNSUPPORTED;
+  if (nsplit + rq.shared_pre > kMaxSplits) return LLM_ERR_UNSUPPORTED;
   const int group = std::max(1, std::min(row_group, 4));  // PaSplitArgs::group
   PaLaunch p;
   p.nsplit = nsplit;
   p.pps = pps_fixed;
-  p.direct = nsplit <= 1;
+  p.direct = nsplit <= 1 && !shared;
   p.wgm = wgm_ok && !p.direct && group == 1 && nsplit <= kWgmMaxSplits;
   p.oproj = oproj && p.wgm;
   p.beam = group == 4 && !p.direct && beam_shape;
@@ -231,7 +240,9 @@ inline int pa_plan(const PaRequest& rq, const PaTuning& tn, long long resident,
   p.steal_ctr = rq.steal_ctr;
   p.merge_row = rq.out == PaOut::ROW_Q || out16;
   p.workspace_bytes =
-      p.direct || p.wgm ? 0 : (size_t)B * H * nsplit * (size_t)(D + 2) * sizeof(float);
+      p.direct || p.wgm
+          ? 0
+          : (size_t)B * H * (nsplit + rq.shared_pre) * (size_t)(D + 2) * sizeof(float);
   *out = p;
   return LLM_OK;
 }

@@ -113,6 +113,14 @@ struct PaSplitArgs {
   // [max(0, T_b - window), T_b) only.  Wave-uniform; row_span below turns it
   // into the row's live tiles.
   int window;
+  // Shared-prefix launches (pa_shared.hip; NULL: off): first_tile[b] = the
+  // leading tiles of row b that the group kernel covers (0: none).  The row's
+  // live tiles start there (row_first below) and its splits are counted from
+  // that tile, as under a window; wave-uniform.  The group kernel's npre
+  // partial slots of every (row, head) sit in front of the nsplit slots the
+  // splits here write.
+  const int32_t* first_tile;
+  int npre;
 };
 
 // Split length of a row with `ntiles` live tiles.
@@ -135,6 +143,12 @@ __device__ __forceinline__ PaSpan row_span(int Tb, int ntiles, int window, int T
   const int t_lo = window > 0 ? max(0, Tb - window) : 0;
   const int lo_tile = t_lo / TS;
   return {t_lo, lo_tile, max(ntiles - lo_tile, 0)};
+}
+// ... of a row whose first `ft` tiles belong to a shared-prefix launch
+// (PaSplitArgs::first_tile; such launches carry no window): tiles ft ..
+// ntiles - 1, every token of them live.  The merges count with this too.
+__device__ __forceinline__ PaSpan row_first(PaSpan s, int ft, int ntiles, int TS) {
+  return {ft * TS, ft, max(ntiles - ft, 0)};
 }
 // Splits of the row that hold a partial: min(nsplit, ceil(n_live / pps)).
 __device__ __forceinline__ int row_nsplits(int pps_fixed, int nsplit, int n_live) {
@@ -326,13 +340,14 @@ void pa_split_kernel(PaSplitArgs a) {
   }
   if (b >= a.B) return;
   const int bh = b * a.H + h;
-  const size_t pidx = (size_t)bh * a.nsplit + s;  // partial-state slot
+  const size_t pidx = (size_t)bh * (a.nsplit + a.npre) + a.npre + s;  // partial-state slot
   const int r = a.beam_ids ? a.beam_ids[b] : b;
   int Tb = a.context_lens ? a.context_lens[b] : a.T;
   Tb = min(max(Tb, 0), a.T);
   const int ntiles = min((Tb + TS - 1) / TS, a.max_tiles);
   // (beam-group launches carry no window: the host refuses it)
-  const PaSpan span = row_span(Tb, ntiles, a.window, TS);
+  PaSpan span = row_span(Tb, ntiles, a.window, TS);
+  if (a.first_tile) span = row_first(span, a.first_tile[b], ntiles, TS);
   const int t_lo = span.t_lo;
   // tiles whose every token is live start at a token in [t_lo, Tb - TS]: one
   // unsigned compare of (tile * TS - t_lo) against this per page

@@ -20,6 +20,7 @@
 #include "pa_tuning.hpp"
 #include "prefill_pack.hpp"
 #include "serve_plan.hpp"
+#include "share_plan.hpp"
 
 namespace llm {
 
@@ -1236,6 +1237,34 @@ extern "C" int serve_prefix_sim_tune(const int32_t* tokens, const int32_t* promp
   }
   if (count > 2147483647LL) return kBad;
   return count > room ? -(int)count : (int)count;
+}
+
+// Tuning hook: the shared-prefix planner (share_plan.hpp) on explicit rows.
+// blocks holds the n rows' chains back to back (nblocks[i] ids each), pos the
+// rows' next positions.  out: per group {G, P, G rows}, in the order the
+// planner took them.  Returns the group count, or < 0 on bad arguments or too
+// little room (3 n + 1 ints always suffice).
+extern "C" int share_plan_sim_tune(const int32_t* blocks, const int32_t* nblocks,
+                                   const int32_t* pos, int n, int page_size, int min_pages,
+                                   int32_t* out, int room) {
+  if (n < 0 || page_size < 1 || min_pages < 0 || !out || (n && (!blocks || !nblocks || !pos)))
+    return -1;
+  std::vector<ShareRow> rows(n);
+  const int32_t* p = blocks;
+  for (int i = 0; i < n; ++i) {
+    if (nblocks[i] < 0 || pos[i] < 0) return -1;
+    rows[i] = ShareRow{p, nblocks[i], pos[i]};
+    p += nblocks[i];
+  }
+  int used = 0;
+  const std::vector<ShareGroup> groups = share_plan(rows, page_size, min_pages);
+  for (const ShareGroup& g : groups) {
+    if (used + 2 + (int)g.rows.size() > room) return -1;
+    out[used++] = (int32_t)g.rows.size();
+    out[used++] = g.tiles;
+    for (int r : g.rows) out[used++] = r;
+  }
+  return (int)groups.size();
 }
 
 // Tuning hook: the beam search's host bookkeeping (beam_plan.hpp) run on

@@ -131,6 +131,12 @@ class LlmPrefixStats(ctypes.Structure):
                  "evicted_blocks", "deferrals")]
 
 
+class LlmSharedStats(ctypes.Structure):
+    """llm_shared_stats of llm_decoder_shared_stats."""
+    _fields_ = [(n, ctypes.c_longlong) for n in ("shared_steps", "grouped_row_steps",
+                                                 "page_reads_saved")]
+
+
 class LlmError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"[llm status {status}] {msg}")
@@ -178,6 +184,15 @@ _SIGS = {
     "pa_decode_ex": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_void_p,
                              c_int, c_int, c_int, c_int, ctypes.POINTER(PaDecodeOptions),
                              c_void_p, c_size_t, c_void_p]),
+    "pa_decode_shared_workspace_bytes": (c_size_t, [ctypes.POINTER(PaKvView), c_int, c_int]),
+    "pa_decode_shared": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_int, c_int, c_float, c_i32p, c_i32p, c_i32p, c_int,
+                                 c_void_p, c_size_t, c_void_p]),
+    # tuning library only: the shared-prefix planner (csrc/share_plan.hpp), host only
+    "share_plan_sim_tune": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_int, c_i32p, c_int]),
+    "llm_decoder_set_shared_attention": (c_int, [c_void_p, c_int]),
+    "llm_decoder_shared_attention": (c_int, [c_void_p]),
+    "llm_decoder_shared_stats": (c_int, [c_void_p, ctypes.POINTER(LlmSharedStats)]),
     "pa_prefill_workspace_bytes": (c_size_t, [ctypes.POINTER(PaKvView), c_int, c_int]),
     "pa_decode_ex_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pa_prefill": (c_int, [ctypes.POINTER(PaKvView), c_void_p, c_int, c_void_p, c_int, c_int,
@@ -472,6 +487,52 @@ def pa_decode(q, k_pool, v_pool, page_table, *, T, beam_ids=None, context_lens=N
                             ptr(context_lens), B, H, D, T, sm_scale, pages_per_split, ptr(ws),
                             ws_bytes, stream_ptr(stream)))
     return out
+
+
+def pa_decode_shared(q, k_pool, v_pool, page_table, *, T, groups, context_lens=None,
+                     sm_scale=1.0, out=None, stream=None):
+    """pa_decode for rows that share leading pages (pa_decode_shared): groups =
+    [(rows, P), ...], each a list of batch rows whose first P tiles map the same
+    pages; returns out [B][H][D] fp32."""
+    import torch
+    lib = load()
+    B, H, D = q.shape
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float32, device=q.device)
+    view = kv_view(k_pool, v_pool, page_table)
+    rows = [int(r) for g, _ in groups for r in g]
+    off = [0]
+    for g, _ in groups:
+        off.append(off[-1] + len(g))
+    arr = lambda v: (ctypes.c_int32 * max(len(v), 1))(*v)
+    ws_bytes = lib.pa_decode_shared_workspace_bytes(ctypes.byref(view), B, T)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    check(lib.pa_decode_shared(ctypes.byref(view), ptr(q), ptr(out), ptr(context_lens), B, H, D,
+                               T, sm_scale, arr(rows), arr(off), arr([int(p) for _, p in groups]),
+                               len(groups), ptr(ws), ws_bytes, stream_ptr(stream)))
+    return out
+
+
+def share_plan_sim(chains, pos, *, page_size, min_pages):
+    """share_plan_sim_tune (tuning library, host only): the shared-prefix groups
+    of rows whose block chains (ServeReq::blocks: the block id of each leading
+    tile) and next positions are given: [(rows, shared tiles), ...] in the
+    order the planner takes them."""
+    tune = load_tune()
+    n = len(chains)
+    flat = [b for c in chains for b in c]
+    arr = lambda v: (ctypes.c_int32 * max(len(v), 1))(*v)
+    out = (ctypes.c_int32 * (3 * n + 1))()
+    ng = tune.share_plan_sim_tune(arr(flat), arr([len(c) for c in chains]), arr(list(pos)), n,
+                                  page_size, min_pages, out, len(out))
+    if ng < 0:
+        raise ValueError("share_plan_sim: bad arguments")
+    groups, i = [], 0
+    for _ in range(ng):
+        g, p = out[i], out[i + 1]
+        groups.append((list(out[i + 2:i + 2 + g]), p))
+        i += 2 + g
+    return groups
 
 
 def pa_decode_plan(k_pool, v_pool, page_table, *, B, T, pages_per_split=0, row_group=1,

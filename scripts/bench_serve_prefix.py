@@ -2,6 +2,11 @@
 """Serving with the prefix cache against serving without it, one process, C3 dims.
 
     python scripts/bench_serve_prefix.py [--out profiles/serve_prefix.json] [--reps 3]
+    python scripts/bench_serve_prefix.py --shared 16 [--out profiles/serve_shared.json]
+
+--shared N adds a third side, "cache_shared": the cache plus shared-prefix
+attention from N shared pages on (llm_decoder_set_shared_attention), with its
+shared_stats() of the last repetition; several N sweep the minimum length.
 
 Arm "shared": 128 requests whose prompts are one 1024-token header plus a
 unique tail of 64..256 tokens, 16..128 new tokens each.  Arm "skewed":
@@ -35,11 +40,24 @@ sys.path.insert(0, str(ROOT / "scripts"))
 from bench_serve import C3, MAXB, timed  # noqa: E402
 
 
-def arm(dec, cfg, name, prompts, max_new, reps, max_seq):
+def arm(dec, cfg, name, prompts, max_new, reps, max_seq, shared=()):
     import llm_capi
     want = sum(max_new)
     sides = {"cache_on": lambda: dec.generate_many(prompts, max_new, prefix_cache=True),
              "cache_off": lambda: dec.generate_many(prompts, max_new)}
+    shared_stats = {}
+
+    def shared_side(n):
+        def run():
+            dec.set_shared_attention(n)
+            try:
+                return dec.generate_many(prompts, max_new, prefix_cache=True)
+            finally:
+                shared_stats[n] = dec.shared_stats()
+                dec.set_shared_attention(0)
+        return run
+    for n in shared:
+        sides[f"cache_shared_{n}"] = shared_side(n)
     for fn in sides.values():  # warm: graphs of every row count, prefill buffers
         fn()
     secs = {k: [] for k in sides}
@@ -59,7 +77,7 @@ def arm(dec, cfg, name, prompts, max_new, reps, max_seq):
         recs, st = llm_capi.serve_prefix_sim(prompts, max_new, max_new, max_rows=MAXB,
                                              num_pages=pages, pages_per_tile=cfg["L"] * cfg["H"],
                                              page_size=cfg["ts"], max_seq_len=max_seq,
-                                             prefix_cache=k == "cache_on")
+                                             prefix_cache=k != "cache_off")
         due = sum(len(p) - 1 for p in prompts)
         med = statistics.median(v)
         res[k] = {"seconds": [round(t, 4) for t in v], "median_s": round(med, 4),
@@ -69,6 +87,10 @@ def arm(dec, cfg, name, prompts, max_new, reps, max_seq):
                   "positions_prefilled": due - st["positions_hit"],
                   "positions_hit": st["positions_hit"],
                   "deferrals": st["deferrals"], "evicted_blocks": st["evicted_blocks"]}
+        if k.startswith("cache_shared_"):
+            res[k]["shared_stats"] = shared_stats[int(k.rsplit("_", 1)[1])]
+            res[k]["same_ids_as_cache_on"] = round(float(np.mean(
+                [a == b for a, b in zip(ids[k], ids["cache_on"])])), 3)
     diff = res["cache_on"]["median_s"] - res["cache_off"]["median_s"]
     res["off_over_on"] = round(res["cache_off"]["median_s"] / res["cache_on"]["median_s"], 3)
     res["on_minus_off_s"] = round(diff, 4)
@@ -83,6 +105,8 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "serve_prefix.json"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--layers", type=int, default=C3["L"])
+    ap.add_argument("--shared", type=int, nargs="*", default=[],
+                    help="minimum shared pages of the cache + shared attention sides")
     args = ap.parse_args()
     import llm_decoder
     from bench import make_weights
@@ -105,8 +129,9 @@ def main():
                       "packed_prefill": True, "reps": args.reps,
                       "timing": "wall clock, device synchronised around every window; sides "
                                 "alternate"},
-           "shared": arm(dec, cfg, "shared", shared, shared_new, args.reps, max_seq),
-           "skewed": arm(dec, cfg, "skewed", skew, skew_new, args.reps, max_seq)}
+           "shared": arm(dec, cfg, "shared", shared, shared_new, args.reps, max_seq, args.shared),
+           "skewed": arm(dec, cfg, "skewed", skew, skew_new, args.reps, max_seq,
+                         args.shared[:1])}
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
 
