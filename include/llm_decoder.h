@@ -45,8 +45,9 @@ enum llm_status {
  * pa_decode / pa_decode_grouped / pa_decode_ex read LLM_FP8 pools as plain
  * numbers (scale 1), as they read LLM_I8: a caller with scales folds K's into
  * sm_scale and multiplies `out` by V's.  The decoder keeps one k_scale and one
- * v_scale per layer (llm_decoder_set_kv_scales). */
-enum llm_dtype { LLM_F16 = 0, LLM_I8 = 1, LLM_F32 = 2, LLM_BF16 = 3, LLM_FP8 = 4 };
+ * v_scale per layer (llm_decoder_set_kv_scales).
+ * LLM_I4 is a weight type only: the 4-bit format of "INT4 weights" below. */
+enum llm_dtype { LLM_F16 = 0, LLM_I8 = 1, LLM_F32 = 2, LLM_BF16 = 3, LLM_FP8 = 4, LLM_I4 = 5 };
 enum llm_act { LLM_ACT_NONE = 0, LLM_ACT_RELU = 1, LLM_ACT_GELU = 2 };
 
 const char* llm_last_error(void);
@@ -357,6 +358,42 @@ int i8_matmul_s8(const int8_t* A, const int8_t* B, int8_t* C, int batch, int M, 
  *   C[m,n] = act(sum_k A[m,k] W[k,n] + bias[n]),  A fp16 [M][K], K % 32 == 0. */
 int f16_gemm(const void* A, int lda, const void* W_packed, float* C, int M, int N, int K,
              const float* bias, int act, void* stream);
+
+/* INT4 weights (LLM_I4): a two-level integer format.  For W [K][N] with
+ * K % 128 == 0, N % 16 == 0, K < 131072:
+ *   q[k][n]  in [-7, 7], 4-bit two's complement; interchange layout uint8
+ *            [K/2][N], byte (k/2, n) = even k in the low nibble, odd k in the high
+ *   m[g][n]  uint8 [K/128][N] in [1, 18]: the multiplier of group g = k / 128
+ *   sw[n]    fp32 per column, as for int8 weights
+ * The expanded weight w8[k][n] = q[k][n] * m[k/128][n] is an int8 (|w8| <= 126),
+ * and w4_gemm is i8_gemm on it, bit for bit:
+ *   acc[m,n] = sum_k int32(A[m,k]) * int32(w8[k,n])         exact int32
+ *   C[m,n]   = act(float(acc) * (sa[m] * sw[n]) + bias[n])  fp32
+ * (products and the add rounded separately).  Device bytes: K*N/2 + K*N/128.
+ *
+ * w4_quantize (host only, deterministic), from per-column int8 W8 [K][N]: per
+ * group and column m = min(18, max(1, ceil(max|W8| / 7))) and q = clamp(rint(
+ * W8 / m), -7, 7), ties to even; a group that some multiplier in [m, 18]
+ * reproduces exactly takes the smallest such multiplier instead, so that
+ * quantising representable weights returns them.  w4_expand (host only)
+ * writes w8.  N need not be a multiple of 16 for these two; K is checked
+ * (a multiple of 128 below 131072). */
+int w4_quantize(const int8_t* W8, int K, int N, uint8_t* q, uint8_t* m);
+int w4_expand(const uint8_t* q, const uint8_t* m, int K, int N, int8_t* W8);
+/* Bytes of the packed device layout (0 for an unsupported K / N), and the
+ * repack from the interchange layout (device -> device): nibbles in MFMA
+ * B-fragment order, then the multipliers per column tile (csrc/gemm_w4.hip). */
+size_t w4_packed_bytes(int K, int N);
+int w4_pack_weights(const uint8_t* q, const uint8_t* m, void* W_packed, int K, int N,
+                    void* stream);
+/* A int8 [M][K]: row-major (a_packed 0, row stride lda >= K, lda % 16 == 0) or
+ * in MFMA A-fragment order (a_packed 1: element (m, k) at ((m/16 * K/64 + k/64)
+ * * 64 + m%16 + 16 * (k%64 / 16)) * 16 + k%16, ceil(M/16) whole row tiles; lda
+ * ignored).  sa / sw / bias may be NULL (1, 1, 0); acc_out (int32 [M][N]) and
+ * C (fp32 [M][N]) may each be NULL.  Any M >= 0. */
+int w4_gemm(const int8_t* A, int lda, int a_packed, const void* W_packed, int32_t* acc_out,
+            float* C, int M, int N, int K, const float* sa, const float* sw, const float* bias,
+            int act, void* stream);
 
 /* Tied-embedding LM head: logits[m,v] = sum_k x[m,k] * E[v,k], x fp32 [M][K],
  * E fp16 [V][K] (token_embedding.hpp layout).  x is split hi+lo into two fp16
@@ -725,11 +762,43 @@ typedef struct llm_f16_weights {
 } llm_f16_weights;
 int llm_decoder_set_f16_weights(llm_decoder* d, const llm_f16_weights* w);
 
+/* INT8 decoder with 4-bit o_proj / fc1 / fc2 weights ("INT4 weights" above;
+ * hidden_dim and inter_dim multiples of 128): wqkv stays int8 with sw_qkv; wo,
+ * w1, w2 arrive as (q, m, sw) in the interchange layout, L consecutive
+ * matrices each.  The decoder then keeps no int8 copy of wo / w1 / w2 on the
+ * device and its layers run them through w4_gemm's kernel (LayerNorm 2 and
+ * the row quantisers as launches of their own); everything else is unchanged.
+ * llm_decoder_set_int8_weights returns the decoder to 8-bit weights. */
+typedef struct llm_w4_weights {
+  const uint16_t* emb;
+  const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+  const int8_t* wqkv; const float* sw_qkv;
+  const uint8_t *wo_q, *wo_m; const float* sw_o;
+  const uint8_t *w1_q, *w1_m; const float* sw1; const float* b1;
+  const uint8_t *w2_q, *w2_m; const float* sw2; const float* b2;
+} llm_w4_weights;
+int llm_decoder_set_w4_weights(llm_decoder* d, const llm_w4_weights* w);
+/* An int8 set, its wo / w1 / w2 quantised to 4 bits on the host (w4_quantize,
+ * layer by layer) and loaded through llm_decoder_set_w4_weights. */
+int llm_decoder_set_int8_weights_int4(llm_decoder* d, const llm_int8_weights* w);
+/* The width of the decoder's o_proj / fc1 / fc2 weights: 4 or 8 for an INT8
+ * decoder, 16 for an FP16 decoder, -1 for NULL. */
+int llm_decoder_weight_bits(const llm_decoder* d);
+/* The device bytes of the layers' four weight matrices, all layers together
+ * (0 before any load). */
+size_t llm_decoder_weight_bytes(const llm_decoder* d);
+/* The int8 wo [L][hid][hid], w1 [L][hid][inter], w2 [L][inter][hid] (host) that
+ * a 4-bit decoder's weights equal, read back from its device copy. */
+int llm_decoder_expanded_weights(llm_decoder* d, int8_t* wo, int8_t* w1, int8_t* w2);
+
 /* CUDADecoder::load_weights (decoder/cuda_decoder.cu:35-45) / INT8Decoder::
  * load_quantized_weights (decoder/int8_decoder.cpp:91-95) / quantize_weights
  * (:43-89) over the raw little-endian .bin layout of weights/README.md:26-38. */
 int llm_decoder_load_weights(llm_decoder* d, const char* dir);
 int llm_decoder_load_quantized_weights(llm_decoder* d, const char* dir);
+/* The same INT8 directory, its o_proj / fc1 / fc2 quantised to 4 bits at load
+ * (llm_decoder_set_int8_weights_int4). */
+int llm_decoder_load_quantized_weights_int4(llm_decoder* d, const char* dir);
 int llm_quantize_weights(const char* fp32_dir, const char* int8_dir, int num_layers,
                          int hidden_dim, int inter_dim, int vocab_size);
 

@@ -92,9 +92,10 @@ class Decoder {
     py::gil_scoped_release nogil;
     check(llm_decoder_load_weights(d_, path.c_str()));
   }
-  void load_quantized_weights(const std::string& path) {
+  void load_quantized_weights(const std::string& path, bool int4) {
     py::gil_scoped_release nogil;
-    check(llm_decoder_load_quantized_weights(d_, path.c_str()));
+    check(int4 ? llm_decoder_load_quantized_weights_int4(d_, path.c_str())
+               : llm_decoder_load_quantized_weights(d_, path.c_str()));
   }
   void quantize_weights(const std::string& src, const std::string& dst) {
     py::gil_scoped_release nogil;
@@ -102,7 +103,11 @@ class Decoder {
                                cfg_.inter_dim, cfg_.vocab_size));
   }
 
-  void set_weights(const py::dict& w) {
+  // int4 (INT8Decoder): o_proj / fc1 / fc2 quantised to 4 bits at load
+  // (llm_decoder_set_int8_weights_int4)
+  void set_weights(const py::dict& w, bool int4) {
+    if (int4 && cfg_.weight_dtype != LLM_I8)
+      throw std::invalid_argument("set_weights: int4 needs an INT8Decoder");
     const size_t L = cfg_.num_layers, hid = cfg_.hidden_dim, inter = cfg_.inter_dim,
                  V = cfg_.vocab_size;
     auto emb = arr<uint16_t>(w, "emb", V * hid);
@@ -118,7 +123,8 @@ class Decoder {
                          wqkv.data(), sq.data(), wo.data(), so.data(), w1.data(), s1.data(),
                          b1.data(), w2.data(), s2.data(), b2.data()};
       py::gil_scoped_release nogil;
-      check(llm_decoder_set_int8_weights(d_, &x));
+      check(int4 ? llm_decoder_set_int8_weights_int4(d_, &x)
+                 : llm_decoder_set_int8_weights(d_, &x));
     } else {
       auto wqkv = arr<uint16_t>(w, "wqkv", L * hid * 3 * hid), wo = arr<uint16_t>(w, "wo", L * hid * hid);
       auto w1 = arr<uint16_t>(w, "w1", L * hid * inter), w2 = arr<uint16_t>(w, "w2", L * inter * hid);
@@ -127,6 +133,19 @@ class Decoder {
       py::gil_scoped_release nogil;
       check(llm_decoder_set_f16_weights(d_, &x));
     }
+  }
+
+  int weight_bits() const { return llm_decoder_weight_bits(d_); }
+  size_t weight_bytes() const { return llm_decoder_weight_bytes(d_); }
+  // the int8 wo / w1 / w2 a 4-bit decoder's weights equal (llm_decoder_expanded_weights)
+  py::dict expanded_weights() {
+    const py::ssize_t L = cfg_.num_layers, hid = cfg_.hidden_dim, inter = cfg_.inter_dim;
+    py::array_t<int8_t> wo({L, hid, hid}), w1({L, hid, inter}), w2({L, inter, hid});
+    check(llm_decoder_expanded_weights(d_, wo.mutable_data(), w1.mutable_data(),
+                                       w2.mutable_data()));
+    py::dict out;
+    out["wo"] = wo; out["w1"] = w1; out["w2"] = w2;
+    return out;
   }
 
   std::vector<std::vector<int>> generate_batch(const std::vector<std::vector<int>>& prompts,
@@ -829,7 +848,10 @@ PYBIND11_MODULE(llm_decoder, m) {
   };
   auto common = [&](auto& c) {
     c.def("load_weights", &Decoder::load_weights, "CUDADecoder::load_weights (fp32 .bin dir)")
-        .def("set_weights", &Decoder::set_weights, py::arg("weights"))
+        .def("set_weights", &Decoder::set_weights, py::arg("weights"), py::arg("int4") = false)
+        .def("weight_bits", &Decoder::weight_bits)
+        .def("weight_bytes", &Decoder::weight_bytes)
+        .def("expanded_weights", &Decoder::expanded_weights)
         .def("generate", &Decoder::generate)
         .def("generate_batch", &Decoder::generate_batch, py::arg("input_ids"),
              py::arg("max_gen_len"), py::arg("temperature") = 1.0f)
@@ -906,7 +928,8 @@ PYBIND11_MODULE(llm_decoder, m) {
          py::arg("inter_dim") = 0, py::arg("attn_scale") = 1.0f, py::arg("num_pages") = 0,
          py::arg("kv_dtype") = "float16");
   common(id);
-  id.def("load_quantized_weights", &Decoder::load_quantized_weights)
+  id.def("load_quantized_weights", &Decoder::load_quantized_weights, py::arg("path"),
+         py::arg("int4") = false)
       .def("quantize_weights", &Decoder::quantize_weights);
 
   py::class_<KVTileCache>(m, "KVTileCache")

@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "gemm.hpp"
+#include "gemm_w4.hpp"
 #include "kv_cache_impl.hpp"
 #include "pa_decode.hpp"
 #include "row_ops.hpp"
@@ -115,6 +116,10 @@ struct llm_decoder {
   DevBuf<uint16_t> wo_heads;
   size_t sz_qkv = 0, sz_o = 0, sz_1 = 0, sz_2 = 0;
   bool weights_ready = false;
+  // llm_decoder_set_w4_weights: wo / w1 / w2 hold the packed 4-bit layout of
+  // csrc/gemm_w4.hip (sz_o / sz_1 / sz_2 its bytes) and layer_post runs them
+  // through w4_weight_gemm on the unfused forms; wqkv stays int8
+  bool w4 = false;
   int w_keep = 0;  // the GEMM weights fit the Infinity Cache: keep them there (w_keep_for)
 
   // KV: fp16 pools, or LLM_FP8 bytes (csrc/fp8.hpp) with one K and one V
@@ -213,11 +218,13 @@ struct llm_decoder {
   int layer_pre(int l, hipStream_t st, const Rows& R, const LnSource* emb = nullptr);
   int layer_attn(int l, hipStream_t st, const Rows& R);
   int attn_request(const Rows& R, pa_kv_view* view, PaRequest* rq, int l = 0);
+  bool quant_prologue_shape(const Rows& R) const;
   bool quant_prologue(const Rows& R) const;
   bool oproj_fusable(const Rows& R);
   bool wgm_quant_ok(const Rows& R);
   bool fc2_split(const Rows& R) const;
   int layer_post(int l, hipStream_t st, const Rows& R);
+  int layer_post_w4(int l, hipStream_t st, const Rows& R);
   int decode_rows(Rows* R, bool scratch_oproj = false);
   int next_tokens(const float* xr, int n, int r0, const int32_t* ctr, hipStream_t st,
                   int32_t* adv_pos = nullptr, int32_t* adv_ctx = nullptr);

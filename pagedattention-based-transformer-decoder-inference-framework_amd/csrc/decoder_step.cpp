@@ -87,10 +87,13 @@ int llm_decoder::layer_norm_into(WeightGemm& g, const Rows& R, const float* gamm
 // the workgroup, and the o_proj prologue quantises them per row -- no merge
 // launch.  Beam groups keep the merge launch (the beam kernel's workgroups
 // are 4 beams of one split), as do prefill chunks.
-bool llm_decoder::quant_prologue(const Rows& R) const {
+bool llm_decoder::quant_prologue_shape(const Rows& R) const {
   return wdtype == LLM_I8 && !R.is_prefill() && R.row_group == 1 &&
          quant_prologue_ok(R.n, hid, hid);
 }
+// (4-bit weights: the W4 kernel has no prologue; the attention writes the
+// packed int8 rows as it does for beam groups and prefill chunks)
+bool llm_decoder::quant_prologue(const Rows& R) const { return !w4 && quant_prologue_shape(R); }
 
 // FP16 decode rows whose o_proj the attention's workgroup merge can run
 // (pa_decode.hip, OPROJ): each (row, head) workgroup multiplies its merged
@@ -120,7 +123,7 @@ bool llm_decoder::oproj_fusable(const Rows& R) {
 // 103 pages -> 8 of 65 merged in the workgroup).
 bool llm_decoder::wgm_quant_ok(const Rows& R) {
   if (wdtype != LLM_I8 || R.is_prefill() || R.row_group != 1 || R.beam_rows || R.shared ||
-      quant_prologue(R))
+      quant_prologue_shape(R))
     return false;
   Rows r = R;
   r.wgm_quant = true;
@@ -142,7 +145,7 @@ bool llm_decoder::wgm_quant_ok(const Rows& R) {
 // workgroup of the one-slice form reads all of A, 1 MB, the k slices half of
 // it (gemm_impl.hpp narrow_decode_tile).
 bool llm_decoder::fc2_split(const Rows& R) const {
-  return wdtype == LLM_I8 && !R.is_prefill() &&
+  return wdtype == LLM_I8 && !w4 && !R.is_prefill() &&
          (R.n <= 16 || (R.n > 32 && R.n <= 64 && inter >= 16384)) &&
          !ln_fusable(wdtype, R.n, hid) && inter / 64 >= 16;
 }
@@ -210,7 +213,43 @@ int llm_decoder::layer_attn(int l, hipStream_t st, const Rows& R) {
   return LLM_OK;
 }
 
+// layer_post with 4-bit o_proj / fc1 / fc2 (llm_decoder_set_w4_weights): the
+// three GEMMs on the W4 kernel, which has no prologue and no k slices, so
+// LayerNorm 2 and both row quantisers are launches of their own -- the forms
+// prefill chunks already run with int8 weights.
+int llm_decoder::layer_post_w4(int l, hipStream_t st, const Rows& R) {
+  const size_t lh = (size_t)l * hid;
+  int8_t* act = static_cast<int8_t*>(R.act);
+  W4Gemm g;
+  g.a_packed = 1;
+  g.w_keep = w_keep;
+  g.A = act;
+  g.M = R.n;
+  g.sa = R.sa;
+  // o_proj: the attention wrote the packed int8 rows and their scales
+  g.W_packed = wo.p + sz_o * l; g.N = hid; g.K = hid; g.C = R.x;
+  g.sw = sw_o.p + lh;
+  RET_IF(w4_weight_gemm(g, st));
+  RET_IF(tap(l, 1, R, hid, st));
+  // LN2 -> mlp_fc1 (+b1, ReLU)
+  LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, nullptr,
+                                     act, R.sa, st, 1, nullptr));
+  g.W_packed = w1.p + sz_1 * l; g.N = inter; g.K = hid; g.C = R.h1;
+  g.sw = sw1.p + (size_t)l * inter;
+  g.bias = b1.p + (size_t)l * inter; g.act = LLM_ACT_RELU;
+  RET_IF(w4_weight_gemm(g, st));
+  RET_IF(tap(l, 2, R, hid, st));
+  // quantise h1 -> mlp_fc2 (+b2)
+  LLM_HIP_RET(launch_quantize_rows(R.h1, R.n, inter, act, R.sa, st, 1));
+  RET_IF(tap(l, 3, R, inter, st));
+  g.W_packed = w2.p + sz_2 * l; g.N = hid; g.K = inter; g.C = R.x;
+  g.sw = sw2.p + lh;
+  g.bias = b2.p + lh; g.act = LLM_ACT_NONE;
+  return w4_weight_gemm(g, st);
+}
+
 int llm_decoder::layer_post(int l, hipStream_t st, const Rows& R) {
+  if (w4) return layer_post_w4(l, st, R);
   const size_t lh = (size_t)l * hid;
   const bool i8 = wdtype == LLM_I8;
   WeightGemm g;

@@ -13,6 +13,7 @@
 
 #include "decoder_impl.hpp"
 #include "oproj_slices.hpp"
+#include "w4_quant.hpp"
 
 // ---------------------------------------------------------------------------
 // weights
@@ -91,9 +92,118 @@ extern "C" int llm_decoder_set_int8_weights(llm_decoder* d, const llm_int8_weigh
   RET_IF(upload(d->sw2, w->sw2, (size_t)L * hid, "sw2"));
   RET_IF(upload(d->b1, w->b1, (size_t)L * inter, "b1"));
   RET_IF(upload(d->b2, w->b2, (size_t)L * hid, "b2"));
+  d->w4 = false;
   d->w_keep = w_keep_for(d);
   d->drop_step_graph();
   d->weights_ready = true;
+  return LLM_OK;
+}
+
+// Upload L interchange-layout 4-bit matrices (q [K/2][N], m [K/128][N]) and
+// pack each into the W4 GEMM's device layout (csrc/gemm_w4.hip).
+static int upload_w4(DevBuf<uint8_t>& dst, size_t& per_layer, const uint8_t* q, const uint8_t* m,
+                     int L, int K, int N, const char* what) {
+  LLM_REQUIRE(q && m, std::string("decoder weights: ") + what + " is NULL");
+  per_layer = w4_packed_bytes(K, N);
+  LLM_REQUIRE(per_layer > 0, std::string("decoder weights: ") + what +
+                                 " needs K % 128 == 0 and N % 16 == 0 for 4-bit weights");
+  RET_IF(dst.alloc(per_layer * L));
+  const size_t qb = (size_t)(K / 2) * N, mb = (size_t)(K / 128) * N;
+  DevBuf<uint8_t> tmp;
+  RET_IF(tmp.alloc(qb + mb));
+  int rc = LLM_OK;
+  for (int l = 0; l < L && rc == LLM_OK; ++l) {
+    if (hipMemcpy(tmp.p, q + qb * l, qb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tmp.p + qb, m + mb * l, mb, hipMemcpyHostToDevice) != hipSuccess) {
+      rc = fail(LLM_ERR_HIP, "decoder weights: upload failed");
+      break;
+    }
+    rc = w4_pack_weights(tmp.p, tmp.p + qb, dst.p + per_layer * l, K, N, nullptr);
+  }
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
+extern "C" int llm_decoder_set_w4_weights(llm_decoder* d, const llm_w4_weights* w) {
+  LLM_REQUIRE(d && w, "llm_decoder_set_w4_weights: NULL");
+  LLM_REQUIRE(d->wdtype == LLM_I8, "llm_decoder_set_w4_weights: decoder is not INT8");
+  LLM_REQUIRE(d->hid % 128 == 0 && d->inter % 128 == 0,
+              "llm_decoder_set_w4_weights: hidden_dim and inter_dim must be multiples of 128");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  const int L = d->L, hid = d->hid, inter = d->inter;
+  d->weights_ready = false;
+  RET_IF(upload_common(d, w->emb, w->ln1_g, w->ln1_b, w->ln2_g, w->ln2_b));
+  RET_IF(upload_packed(d->wqkv, d->sz_qkv, w->wqkv, L, hid, 3 * hid, LLM_I8, "wqkv"));
+  RET_IF(upload_w4(d->wo, d->sz_o, w->wo_q, w->wo_m, L, hid, hid, "wo"));
+  RET_IF(upload_w4(d->w1, d->sz_1, w->w1_q, w->w1_m, L, hid, inter, "w1"));
+  RET_IF(upload_w4(d->w2, d->sz_2, w->w2_q, w->w2_m, L, inter, hid, "w2"));
+  RET_IF(upload(d->sw_qkv, w->sw_qkv, (size_t)L * 3 * hid, "sw_qkv"));
+  RET_IF(upload(d->sw_o, w->sw_o, (size_t)L * hid, "sw_o"));
+  RET_IF(upload(d->sw1, w->sw1, (size_t)L * inter, "sw1"));
+  RET_IF(upload(d->sw2, w->sw2, (size_t)L * hid, "sw2"));
+  RET_IF(upload(d->b1, w->b1, (size_t)L * inter, "b1"));
+  RET_IF(upload(d->b2, w->b2, (size_t)L * hid, "b2"));
+  d->w4 = true;
+  d->w_keep = w_keep_for(d);
+  d->drop_step_graph();
+  d->weights_ready = true;
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_set_int8_weights_int4(llm_decoder* d, const llm_int8_weights* w) {
+  LLM_REQUIRE(d && w, "llm_decoder_set_int8_weights_int4: NULL");
+  LLM_REQUIRE(d->wdtype == LLM_I8, "llm_decoder_set_int8_weights_int4: decoder is not INT8");
+  LLM_REQUIRE(d->hid % 128 == 0 && d->inter % 128 == 0,
+              "llm_decoder_set_int8_weights_int4: hidden_dim and inter_dim must be multiples "
+              "of 128");
+  LLM_REQUIRE(w->wo && w->w1 && w->w2, "llm_decoder_set_int8_weights_int4: NULL weights");
+  const int L = d->L, hid = d->hid, inter = d->inter;
+  struct { const int8_t* w8; int K, N; std::vector<uint8_t> q, m; } mats[3] = {
+      {w->wo, hid, hid, {}, {}}, {w->w1, hid, inter, {}, {}}, {w->w2, inter, hid, {}, {}}};
+  for (auto& mt : mats) {
+    const size_t kn = (size_t)mt.K * mt.N;
+    mt.q.resize(kn / 2 * L);
+    mt.m.resize(kn / 128 * L);
+    for (int l = 0; l < L; ++l)
+      RET_IF(w4_quantize(mt.w8 + kn * l, mt.K, mt.N, mt.q.data() + kn / 2 * l,
+                         mt.m.data() + kn / 128 * l));
+  }
+  llm_w4_weights y{w->emb, w->ln1_g, w->ln1_b, w->ln2_g, w->ln2_b, w->wqkv, w->sw_qkv,
+                   mats[0].q.data(), mats[0].m.data(), w->sw_o,
+                   mats[1].q.data(), mats[1].m.data(), w->sw1, w->b1,
+                   mats[2].q.data(), mats[2].m.data(), w->sw2, w->b2};
+  return llm_decoder_set_w4_weights(d, &y);
+}
+
+extern "C" int llm_decoder_weight_bits(const llm_decoder* d) {
+  if (!d) return -1;
+  return d->w4 ? 4 : d->wdtype == LLM_I8 ? 8 : 16;
+}
+
+extern "C" size_t llm_decoder_weight_bytes(const llm_decoder* d) {
+  if (!d || !d->weights_ready) return 0;
+  return (d->sz_qkv + d->sz_o + d->sz_1 + d->sz_2) * (size_t)d->L;
+}
+
+extern "C" int llm_decoder_expanded_weights(llm_decoder* d, int8_t* wo, int8_t* w1, int8_t* w2) {
+  LLM_REQUIRE(d && wo && w1 && w2, "llm_decoder_expanded_weights: NULL");
+  LLM_REQUIRE(d->w4 && d->weights_ready,
+              "llm_decoder_expanded_weights: the decoder holds no 4-bit weights");
+  std::lock_guard<std::mutex> g(d->mu);
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  const int hid = d->hid, inter = d->inter;
+  struct { const DevBuf<uint8_t>* buf; size_t sz; int K, N; int8_t* out; } mats[3] = {
+      {&d->wo, d->sz_o, hid, hid, wo}, {&d->w1, d->sz_1, hid, inter, w1},
+      {&d->w2, d->sz_2, inter, hid, w2}};
+  std::vector<uint8_t> host;
+  for (auto& mt : mats) {
+    host.resize(mt.sz);
+    for (int l = 0; l < d->L; ++l) {
+      LLM_HIP_RET(hipMemcpy(host.data(), mt.buf->p + mt.sz * l, mt.sz, hipMemcpyDeviceToHost));
+      w4_unpack_host(host.data(), mt.K, mt.N, mt.out + (size_t)l * mt.K * mt.N);
+    }
+  }
   return LLM_OK;
 }
 
@@ -319,7 +429,8 @@ extern "C" int llm_quantize_weights(const char* fp32_dir, const char* int8_dir, 
   return LLM_OK;
 }
 
-extern "C" int llm_decoder_load_quantized_weights(llm_decoder* d, const char* dir) {
+// int4: o_proj / fc1 / fc2 quantised to 4 bits (w4_quantize) before the upload
+static int load_int8_dir(llm_decoder* d, const char* dir, bool int4) {
   LLM_REQUIRE(d && dir, "llm_decoder_load_quantized_weights: NULL");
   LLM_REQUIRE(d->wdtype == LLM_I8, "llm_decoder_load_quantized_weights: decoder is not INT8");
   const int L = d->L, hid = d->hid, inter = d->inter, V = d->V;
@@ -359,5 +470,13 @@ extern "C" int llm_decoder_load_quantized_weights(llm_decoder* d, const char* di
   llm_int8_weights w{emb.data(), g1.data(), be1.data(), g2.data(), be2.data(), qqkv.data(),
                      sqkv.data(), qo.data(), so.data(), q1.data(), s1.data(), b1.data(),
                      q2.data(), s2.data(), b2.data()};
-  return llm_decoder_set_int8_weights(d, &w);
+  return int4 ? llm_decoder_set_int8_weights_int4(d, &w) : llm_decoder_set_int8_weights(d, &w);
+}
+
+extern "C" int llm_decoder_load_quantized_weights(llm_decoder* d, const char* dir) {
+  return load_int8_dir(d, dir, false);
+}
+
+extern "C" int llm_decoder_load_quantized_weights_int4(llm_decoder* d, const char* dir) {
+  return load_int8_dir(d, dir, true);
 }

@@ -21,7 +21,7 @@ TUNE_LIB_PATH = HERE / "libllm_decoder_hip_tune.so"  # `make tune`: A/B hooks, n
 
 (LLM_OK, LLM_ERR_INVALID, LLM_ERR_UNSUPPORTED, LLM_ERR_HIP, LLM_ERR_OOM, LLM_ERR_IO,
  LLM_ERR_RANGE) = range(7)
-LLM_F16, LLM_I8, LLM_F32, LLM_BF16, LLM_FP8 = 0, 1, 2, 3, 4
+LLM_F16, LLM_I8, LLM_F32, LLM_BF16, LLM_FP8, LLM_I4 = 0, 1, 2, 3, 4, 5
 LLM_ACT_NONE, LLM_ACT_RELU, LLM_ACT_GELU = 0, 1, 2
 LLM_EVICT_NONE, LLM_EVICT_LRU = 0, 1
 
@@ -216,6 +216,19 @@ _SIGS = {
     "gemm_pack_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "i8_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                         c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    # INT4 weights (csrc/gemm_w4.hip, csrc/w4_quant.cpp)
+    "w4_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "w4_expand": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "w4_packed_bytes": (c_size_t, [c_int, c_int]),
+    "w4_pack_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "w4_gemm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                        c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "llm_decoder_set_w4_weights": (c_int, [c_void_p, c_void_p]),
+    "llm_decoder_set_int8_weights_int4": (c_int, [c_void_p, c_void_p]),
+    "llm_decoder_weight_bits": (c_int, [c_void_p]),
+    "llm_decoder_weight_bytes": (c_size_t, [c_void_p]),
+    "llm_decoder_expanded_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "llm_decoder_load_quantized_weights_int4": (c_int, [c_void_p, ctypes.c_char_p]),
     "i8_matmul_s8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                              c_float, c_float, c_void_p, c_int, c_void_p]),
     "f16_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
@@ -775,6 +788,58 @@ def i8_gemm(A, W_packed, N, *, sa=None, sw=None, bias=None, act=0, want_acc=True
     C = torch.empty((M, N), dtype=torch.float32, device=A.device)
     check(lib.i8_gemm(ptr(A), A.stride(0), ptr(W_packed), ptr(acc), ptr(C), M, N, K, ptr(sa),
                       ptr(sw), ptr(bias), act, stream_ptr(stream)))
+    return acc, C
+
+
+def w4_quantize(W8):
+    """Host quantiser of the 4-bit weight format: int8 numpy [K][N] -> (q uint8
+    [K/2][N], m uint8 [K/128][N]) in the interchange layout."""
+    import numpy as np
+    W8 = np.ascontiguousarray(W8, np.int8)
+    K, N = W8.shape
+    q = np.empty((K // 2, N), np.uint8)
+    m = np.empty((K // 128, N), np.uint8)
+    check(load().w4_quantize(W8.ctypes.data, K, N, q.ctypes.data, m.ctypes.data))
+    return q, m
+
+
+def w4_expand(q, m):
+    """The int8 numpy [K][N] that (q, m) stand for: q * m per group of 128."""
+    import numpy as np
+    q, m = np.ascontiguousarray(q, np.uint8), np.ascontiguousarray(m, np.uint8)
+    K, N = 2 * q.shape[0], q.shape[1]
+    W8 = np.empty((K, N), np.int8)
+    check(load().w4_expand(q.ctypes.data, m.ctypes.data, K, N, W8.ctypes.data))
+    return W8
+
+
+def w4_pack_weights(q, m, stream=None):
+    """Repack device (q, m) tensors of the interchange layout into the W4 GEMM's layout."""
+    import torch
+    lib = load()
+    K, N = 2 * q.shape[0], q.shape[1]
+    nbytes = lib.w4_packed_bytes(K, N)
+    if nbytes == 0:
+        raise LlmError(LLM_ERR_INVALID, "w4_pack_weights: K % 128 == 0 and N % 16 == 0 required")
+    P = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    check(lib.w4_pack_weights(ptr(q), ptr(m), ptr(P), K, N, stream_ptr(stream)))
+    return P
+
+
+def w4_gemm(A, W_packed, N, *, M=None, K=None, sa=None, sw=None, bias=None, act=0,
+            want_acc=True, stream=None):
+    """w4_gemm over device tensors.  A: int8 [M][K] (row-major, any row stride),
+    or with M and K given a flat int8 tensor in packed-A order."""
+    import torch
+    lib = load()
+    packed = M is not None
+    if not packed:
+        M, K = A.shape
+    acc = torch.empty((M, N), dtype=torch.int32, device=A.device) if want_acc else None
+    C = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    check(lib.w4_gemm(ptr(A), 0 if packed else A.stride(0), 1 if packed else 0, ptr(W_packed),
+                      ptr(acc), ptr(C), M, N, K, ptr(sa), ptr(sw), ptr(bias), act,
+                      stream_ptr(stream)))
     return acc, C
 
 
