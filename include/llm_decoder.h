@@ -485,6 +485,27 @@ int lm_head_logprobs(const float* x, const void* E, const int32_t* targets, floa
 #define LLM_MAX_TOP_LOGPROBS 8
 int logprob_rows(const float* logits, int rows, int V, const int32_t* chosen, int top_n,
                  float* chosen_lp, float* top_lp, int32_t* top_id, float* stats, void* stream);
+/* The streaming forms of sample_rows, sample_rows_each and logprob_rows
+ * (csrc/sample_wide.hip): the same arguments, the same semantics and the same
+ * draw, for any 1 <= V <= 1048576.  One workgroup per row still, but the row is
+ * not held: it is streamed from memory in a few passes (running max / sum; a
+ * digit-histogram radix select of the top-k and top-p thresholds with the mass
+ * in exact fixed point, p * 2^40; the draw over per-tile sums), so a token is
+ * the same on every launch and graph replay.  A kept probability below 2^-40
+ * cannot be drawn.  logprob_rows_wide keeps each thread's top-n while it
+ * streams and merges the lists: one pass.  These entries ALWAYS run the
+ * streaming kernels; the decoder takes them for vocab_size > 65536 and the
+ * row-holding kernels below that.  LLM_ERR_INVALID on the host for rows < 0,
+ * V outside 1 .. 1048576, a NULL pointer the arguments require, and
+ * sample_rows' / logprob_rows' checks of top_k, top_p and top_n. */
+int sample_rows_wide(const float* logits, int rows, int V, float temperature, int top_k,
+                     float top_p, uint64_t seed, int counter, int32_t* out, void* stream);
+int sample_rows_each_wide(const float* logits, int rows, int V, const float* temperature,
+                          const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                          const int32_t* counter, int32_t* out, void* stream);
+int logprob_rows_wide(const float* logits, int rows, int V, const int32_t* chosen, int top_n,
+                      float* chosen_lp, float* top_lp, int32_t* top_id, float* stats,
+                      void* stream);
 /* The uniform draw sample_rows uses for (seed, row, counter): splitmix64 of
  * seed ^ (row << 32) ^ counter, top 24 bits / 2^24. */
 float sample_uniform_host(uint64_t seed, int row, int counter);
@@ -959,7 +980,8 @@ typedef struct llm_serve_event {
 } llm_serve_event;
 /* Enter serving mode: the cache and the rows are cleared (row_group 1), ids
  * count up from 0 again.  LLM_ERR_UNSUPPORTED in beam mode or with
- * vocab_size > 65536 (every row's token is chosen by sample_rows_each),
+ * vocab_size > 1048576 (every row's token is chosen by sample_rows_each, past
+ * 65536 by its streaming form),
  * LLM_ERR_INVALID if already serving or without weights.  While serving,
  * llm_decoder_generate, _beam_search, _begin_synthetic, _begin_beams,
  * _prefill, _prefill_rows, _step and the setters _set_sampling, _set_window,

@@ -344,8 +344,8 @@ extern "C" int llm_decoder_begin_beams(llm_decoder* d, int num_seqs, int beam_wi
 extern "C" int llm_decoder_set_sampling(llm_decoder* d, float temperature, int top_k, float top_p,
                                         uint64_t seed) {
   LLM_REQUIRE(d, "llm_decoder_set_sampling: NULL");
-  LLM_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && d->V <= 65536,
-              "llm_decoder_set_sampling: top_k >= 0, 0 < top_p <= 1, vocab <= 65536");
+  LLM_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && d->V <= (1 << 20),
+              "llm_decoder_set_sampling: top_k >= 0, 0 < top_p <= 1, vocab <= 1048576");
   std::lock_guard<std::mutex> g(d->mu);
   NOT_SERVING(d, "llm_decoder_set_sampling");
   LLM_HIP_RET(hipStreamSynchronize(d->stream));

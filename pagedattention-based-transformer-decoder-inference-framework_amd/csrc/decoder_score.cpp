@@ -38,8 +38,6 @@ int llm_decoder::score(const int32_t* toks, const int32_t* lens, int stride, int
                 "llm_decoder_score: a sequence needs " + std::to_string(need[s]) +
                     " pages, the pool has " + std::to_string(geom.num_pages));
   }
-  if (score_form == 1 && V > 65536)
-    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_score: LLM_SCORE_FORM=1 needs vocab_size <= 65536");
   if (!lp_val.p) {
     RET_IF(lp_val.alloc(kPrefillChunk));
     LLM_HIP_RET(hipMemset(lp_val.p, 0, sizeof(float) * kPrefillChunk));

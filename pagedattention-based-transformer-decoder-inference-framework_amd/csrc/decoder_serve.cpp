@@ -184,8 +184,8 @@ static int serve_begin(llm_decoder* d, bool prefix_cache) {
   // holds the mutex; the test states the entry's contract)
   if (d->beam_mode)
     return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin: the decoder is in beam mode");
-  if (d->V > 65536)
-    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin: vocab_size > 65536 (the rows' "
+  if (d->V > (1 << 20))
+    return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin: vocab_size > 1048576 (the rows' "
                                      "tokens are chosen by sample_rows_each)");
   if (prefix_cache && d->window > 0)
     return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_serve_begin_opts: prefix_cache with a sliding "

@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "row_ops.hpp"
 #include "row_vals.hpp"
+#include "sample_args.hpp"
 
 namespace llm {
 
@@ -96,6 +97,9 @@ static hipError_t launch_logprob_rows_vpt(const float* logits, int rows, int V,
 hipError_t launch_logprob_rows(const float* logits, int rows, int V, const int32_t* chosen,
                                int top_n, float* chosen_lp, float* top_lp, int32_t* top_id,
                                float* stats, hipStream_t st) {
+  if (V > 128 * kSampleThreads)  // the streaming kernel (csrc/sample_wide.hip)
+    return launch_logprob_rows_wide(logits, rows, V, chosen, top_n, chosen_lp, top_lp, top_id,
+                                    stats, st);
   const int vpt = (V + kSampleThreads - 1) / kSampleThreads;
   if (vpt <= 16)
     return launch_logprob_rows_vpt<16>(logits, rows, V, chosen, top_n, chosen_lp, top_lp, top_id, stats, st);

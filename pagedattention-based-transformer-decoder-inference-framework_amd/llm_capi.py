@@ -243,6 +243,12 @@ _SIGS = {
                             c_int, c_void_p, c_void_p]),
     "sample_rows_each": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "sample_rows_wide": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, ctypes.c_uint64,
+                                 c_int, c_void_p, c_void_p]),
+    "sample_rows_each_wide": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "logprob_rows_wide": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
     "sample_uniform_host": (c_float, [ctypes.c_uint64, c_int, c_int]),
     # continuous batching (llm_decoder_serve_*)
     "llm_decoder_serve_begin": (c_int, [c_void_p]),
@@ -899,10 +905,10 @@ def lm_head_logprobs(x, E, targets, want_stats=True, stream=None):
     return lp, stats
 
 
-def logprob_rows(logits, chosen=None, top_n=0, want_stats=True, stream=None):
+def logprob_rows(logits, chosen=None, top_n=0, want_stats=True, stream=None, wide=False):
     """logprob_rows on torch device tensors: fp32 logits [R][V], chosen int32 [R]
     or None -> (chosen_lp [R] or None, top_lp [R][top_n], top_id [R][top_n],
-    stats [R][2] = {m, lse} or None)."""
+    stats [R][2] = {m, lse} or None).  wide: logprob_rows_wide (V <= 2^20)."""
     import torch
     lib = load()
     R, V = logits.shape
@@ -911,8 +917,9 @@ def logprob_rows(logits, chosen=None, top_n=0, want_stats=True, stream=None):
     tlp = torch.empty((R, top_n), dtype=torch.float32, device=dev)
     tid = torch.empty((R, top_n), dtype=torch.int32, device=dev)
     stats = torch.empty((R, 2), dtype=torch.float32, device=dev) if want_stats else None
-    check(lib.logprob_rows(ptr(logits), R, V, ptr(chosen), top_n, ptr(clp), ptr(tlp), ptr(tid),
-                           ptr(stats), stream_ptr(stream)))
+    fn = lib.logprob_rows_wide if wide else lib.logprob_rows
+    check(fn(ptr(logits), R, V, ptr(chosen), top_n, ptr(clp), ptr(tlp), ptr(tid), ptr(stats),
+             stream_ptr(stream)))
     return clp, tlp, tid, stats
 
 
@@ -925,28 +932,33 @@ def argmax_rows(logits, stream=None):
     return out
 
 
-def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0, stream=None):
-    """Device sampling of one token per row of fp32 logits [R][V] -> int32 [R]."""
+def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, counter=0, stream=None,
+                wide=False):
+    """Device sampling of one token per row of fp32 logits [R][V] -> int32 [R].
+    wide: sample_rows_wide, the streaming kernel (V <= 2^20)."""
     import torch
     lib = load()
     R, V = logits.shape
     out = torch.empty(R, dtype=torch.int32, device=logits.device)
-    check(lib.sample_rows(ptr(logits), R, V, temperature, top_k, top_p, seed, counter, ptr(out),
-                          stream_ptr(stream)))
+    fn = lib.sample_rows_wide if wide else lib.sample_rows
+    check(fn(ptr(logits), R, V, temperature, top_k, top_p, seed, counter, ptr(out),
+             stream_ptr(stream)))
     return out
 
 
 def sample_rows_each(logits, temperature=None, top_k=None, top_p=None, seed=None, counter=None,
-                     stream=None):
+                     stream=None, wide=False):
     """sample_rows_each on torch device tensors: fp32 logits [R][V] and per-row
     device arrays (temperature / top_p float32, top_k / counter int32, seed
-    int64 holding the uint64 bits; None: the entry's default) -> int32 [R]."""
+    int64 holding the uint64 bits; None: the entry's default) -> int32 [R].
+    wide: sample_rows_each_wide."""
     import torch
     lib = load()
     R, V = logits.shape
     out = torch.empty(R, dtype=torch.int32, device=logits.device)
-    check(lib.sample_rows_each(ptr(logits), R, V, ptr(temperature), ptr(top_k), ptr(top_p),
-                               ptr(seed), ptr(counter), ptr(out), stream_ptr(stream)))
+    fn = lib.sample_rows_each_wide if wide else lib.sample_rows_each
+    check(fn(ptr(logits), R, V, ptr(temperature), ptr(top_k), ptr(top_p), ptr(seed), ptr(counter),
+             ptr(out), stream_ptr(stream)))
     return out
 
 
