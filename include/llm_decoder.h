@@ -49,6 +49,10 @@ enum llm_status {
  * LLM_I4 is a weight type only: the 4-bit format of "INT4 weights" below. */
 enum llm_dtype { LLM_F16 = 0, LLM_I8 = 1, LLM_F32 = 2, LLM_BF16 = 3, LLM_FP8 = 4, LLM_I4 = 5 };
 enum llm_act { LLM_ACT_NONE = 0, LLM_ACT_RELU = 1, LLM_ACT_GELU = 2 };
+/* The decoder's MLP (llm_decoder_set_mlp) and the activation of the gated
+ * GEMMs: plain fc2(relu(fc1(x) + b1)) + b2, or gated
+ * fc2(act(gate(x)) * up(x)) + b2 with act = SiLU (SwiGLU) or erf-GELU (GeGLU). */
+enum llm_mlp { LLM_MLP_PLAIN = 0, LLM_MLP_GATED_SILU = 1, LLM_MLP_GATED_GELU = 2 };
 
 const char* llm_last_error(void);
 int llm_abi_version(void);
@@ -358,6 +362,33 @@ int i8_matmul_s8(const int8_t* A, const int8_t* B, int8_t* C, int batch, int M, 
  *   C[m,n] = act(sum_k A[m,k] W[k,n] + bias[n]),  A fp16 [M][K], K % 32 == 0. */
 int f16_gemm(const void* A, int lda, const void* W_packed, float* C, int M, int N, int K,
              const float* bias, int act, void* stream);
+
+/* Gated MLP (SwiGLU / GeGLU) in one launch (csrc/gemm_gated.hip): two packed
+ * weights of the same [K][N] shape (gemm_pack_weights, unchanged), one pass
+ * over A, and
+ *   G[m,n] = float(acc_gate) * (sa[m] * sw_gate[n]) + b_gate[n]
+ *   U[m,n] = float(acc_up)   * (sa[m] * sw_up[n])   + b_up[n]
+ *   H[m,n] = act(G) * U      act: g / (1 + exp(-g)) (LLM_MLP_GATED_SILU) or
+ *                                 LLM_ACT_GELU's function (LLM_MLP_GATED_GELU)
+ * every operation rounded once in fp32; G and U are never stored.  The int32
+ * sums are exact; acc_gate / acc_up (int32 [M][N]) return them.  f16_gemm_gated:
+ * G and U are the fp32 accumulators plus bias.  A as for w4_gemm: row-major
+ * (a_packed 0, row stride lda >= K elements, a multiple of 16 bytes) or in MFMA
+ * A-fragment order (a_packed 1, ceil(M/16) whole row tiles, lda ignored; fp16:
+ * element (m, k) at ((m/16 * K/32 + k/32) * 64 + m%16 + 16 * (k%32 / 8)) * 8 +
+ * k%8).  Outputs, each may be NULL: H fp32 [M][N]; H16, the fp16 rounding of H
+ * in A-fragment order with ceil(N/32) k-steps per row tile (what f16_gemm's
+ * kernel reads as a packed A of K = N; bytes ceil(M/16) * ceil(N/32) * 1024,
+ * elements with n >= N are not written).  sa / sw_* / b_* may be NULL (1, 1,
+ * 0).  Any M >= 0.  K % 64 (fp16: 32) != 0 or N % 16 != 0: LLM_ERR_UNSUPPORTED;
+ * any other bad argument LLM_ERR_INVALID; both before any launch. */
+int i8_gemm_gated(const int8_t* A, int lda, int a_packed, const void* Wg_packed,
+                  const void* Wu_packed, int32_t* acc_gate, int32_t* acc_up, float* H, void* H16,
+                  int M, int N, int K, const float* sa, const float* sw_gate, const float* sw_up,
+                  const float* b_gate, const float* b_up, int mlp, void* stream);
+int f16_gemm_gated(const void* A, int lda, int a_packed, const void* Wg_packed,
+                   const void* Wu_packed, float* H, void* H16, int M, int N, int K,
+                   const float* b_gate, const float* b_up, int mlp, void* stream);
 
 /* INT4 weights (LLM_I4): a two-level integer format.  For W [K][N] with
  * K % 128 == 0, N % 16 == 0, K < 131072:
@@ -751,6 +782,30 @@ int llm_decoder_rope(const llm_decoder* d);
 int llm_decoder_set_window(llm_decoder* d, int window);
 /* The decoder's window (0: off), -1 for NULL. */
 int llm_decoder_window(const llm_decoder* d);
+/* The decoder's MLP (enum llm_mlp; LLM_MLP_PLAIN by default).  With a gated
+ * kind every layer's MLP is down(act(gate(x)) * up(x)) + b2: w1 / sw1 / b1 of
+ * the weight set are the gate, llm_decoder_set_up_weights supplies the up
+ * matrix, w2 / sw2 / b2 are the down projection.  LayerNorm 2 is then a launch
+ * of its own, the gated kernel (i8_gemm_gated / f16_gemm_gated) follows it,
+ * then (INT8) the row quantiser and fc2 as before -- in decode steps, prompt
+ * chunks, packed prefill passes, scoring, serving and beam search alike.
+ * Activation taps: stage 2 is the gated kernel's input, stage 3 fc2's input.
+ * Allowed only before any weights are set and while no rows are active, else
+ * LLM_ERR_INVALID (an unknown kind too).  With a gated kind, 4-bit weights
+ * (llm_decoder_set_w4_weights, .._int8_weights_int4, .._load_quantized_weights
+ * _int4) return LLM_ERR_UNSUPPORTED, and every entry that would start rows
+ * (begin_*, generate, beam search, prefill, score, serve_begin, step) returns
+ * LLM_ERR_INVALID until the up matrix is loaded. */
+int llm_decoder_set_mlp(llm_decoder* d, int kind);
+/* The decoder's enum llm_mlp, -1 for NULL. */
+int llm_decoder_mlp(const llm_decoder* d);
+/* The up matrix of a gated MLP, host arrays: w_up [L][hid][inter] int8 with
+ * sw_up [L][inter] (INT8 decoder) or fp16 with sw_up ignored (FP16 decoder);
+ * b_up [L][inter] fp32 or NULL (no bias).  LLM_ERR_INVALID on a plain-MLP
+ * decoder, while rows are active or serving. */
+int llm_decoder_set_up_weights(llm_decoder* d, const void* w_up, const float* sw_up,
+                               const float* b_up);
+
 /* The attention kernel prompt chunks (llm_decoder_prefill, the prompts of
  * llm_decoder_generate) of this decoder's pools take: LLM_PREFILL_MFMA
  * (pa_prefill: fp16 or LLM_FP8 pools, head_dim 64 or 128, page_size 16 or 32)
@@ -805,8 +860,8 @@ int llm_decoder_set_int8_weights_int4(llm_decoder* d, const llm_int8_weights* w)
 /* The width of the decoder's o_proj / fc1 / fc2 weights: 4 or 8 for an INT8
  * decoder, 16 for an FP16 decoder, -1 for NULL. */
 int llm_decoder_weight_bits(const llm_decoder* d);
-/* The device bytes of the layers' four weight matrices, all layers together
- * (0 before any load). */
+/* The device bytes of the layers' four weight matrices (five with a gated
+ * MLP's up matrix loaded), all layers together (0 before any load). */
 size_t llm_decoder_weight_bytes(const llm_decoder* d);
 /* The int8 wo [L][hid][hid], w1 [L][hid][inter], w2 [L][inter][hid] (host) that
  * a 4-bit decoder's weights equal, read back from its device copy. */
@@ -822,6 +877,14 @@ int llm_decoder_load_quantized_weights(llm_decoder* d, const char* dir);
 int llm_decoder_load_quantized_weights_int4(llm_decoder* d, const char* dir);
 int llm_quantize_weights(const char* fp32_dir, const char* int8_dir, int num_layers,
                          int hidden_dim, int inter_dim, int vocab_size);
+/* Gated MLP: the loaders above also read the up matrix, named as w1's files
+ * are: layer_i/mlp_up.bin [hid][inter] fp32 (llm_decoder_load_weights; an INT8
+ * decoder quantises it per column like w1) or layer_i/mlp_up.i8 + mlp_up.scale
+ * (llm_decoder_load_quantized_weights), and an optional layer_i/mlp_up_bias.bin
+ * [inter] fp32 (absent: no bias).  A gated decoder whose directory lacks the
+ * up files gets LLM_ERR_IO.  llm_quantize_weights does not write the up
+ * matrix: a source directory that holds layer_0/mlp_up.bin is refused with
+ * LLM_ERR_UNSUPPORTED. */
 
 /* Batched generate (CUDADecoder<T>::generate, decoder/cuda_decoder.cu:48-61,
  * batched): for each row, prompt tokens are consumed one per step (KV is

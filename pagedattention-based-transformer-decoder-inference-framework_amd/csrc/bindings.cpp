@@ -133,6 +133,34 @@ class Decoder {
       py::gil_scoped_release nogil;
       check(llm_decoder_set_f16_weights(d_, &x));
     }
+    // gated MLP (set_mlp): the up matrix beside w1 (the gate); b_up optional
+    if (w.contains("w_up")) {
+      py::array_t<float, py::array::c_style | py::array::forcecast> bu;
+      if (w.contains("b_up")) bu = arr<float>(w, "b_up", L * inter);
+      const float* bup = w.contains("b_up") ? bu.data() : nullptr;
+      if (cfg_.weight_dtype == LLM_I8) {
+        auto wu = arr<int8_t>(w, "w_up", L * hid * inter);
+        auto su = arr<float>(w, "sw_up", L * inter);
+        check(llm_decoder_set_up_weights(d_, wu.data(), su.data(), bup));
+      } else {
+        auto wu = arr<uint16_t>(w, "w_up", L * hid * inter);
+        check(llm_decoder_set_up_weights(d_, wu.data(), nullptr, bup));
+      }
+    }
+  }
+
+  // llm_decoder_set_mlp: "plain", "gated_silu" or "gated_gelu"
+  void set_mlp(const std::string& kind) {
+    const int k = kind == "plain" ? LLM_MLP_PLAIN
+                  : kind == "gated_silu" ? LLM_MLP_GATED_SILU
+                  : kind == "gated_gelu" ? LLM_MLP_GATED_GELU
+                                         : -1;
+    if (k < 0) throw std::invalid_argument("set_mlp: 'plain', 'gated_silu' or 'gated_gelu'");
+    check(llm_decoder_set_mlp(d_, k));
+  }
+  std::string mlp() const {
+    const int k = llm_decoder_mlp(d_);
+    return k == LLM_MLP_GATED_SILU ? "gated_silu" : k == LLM_MLP_GATED_GELU ? "gated_gelu" : "plain";
   }
 
   int weight_bits() const { return llm_decoder_weight_bits(d_); }
@@ -904,6 +932,8 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def("set_rope", &Decoder::set_rope, py::arg("table") = py::ellipsis(),
              py::arg("theta") = 10000.0)
         .def_property_readonly("rope", &Decoder::rope)
+        .def("set_mlp", &Decoder::set_mlp, py::arg("kind"))
+        .def_property_readonly("mlp", &Decoder::mlp)
         .def("set_window", &Decoder::set_window, py::arg("window"))
         .def_property_readonly("window", &Decoder::window)
         .def("set_shared_attention", &Decoder::set_shared_attention, py::arg("min_pages") = -1)

@@ -194,6 +194,23 @@ extern "C" int llm_decoder_set_rope(llm_decoder* d, const float* table) {
 
 extern "C" int llm_decoder_rope(const llm_decoder* d) { return d ? (d->rope_on ? 1 : 0) : -1; }
 
+extern "C" int llm_decoder_set_mlp(llm_decoder* d, int kind) {
+  LLM_REQUIRE(d, "llm_decoder_set_mlp: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  NOT_SERVING(d, "llm_decoder_set_mlp");
+  LLM_REQUIRE(kind == LLM_MLP_PLAIN || kind == LLM_MLP_GATED_SILU || kind == LLM_MLP_GATED_GELU,
+              "llm_decoder_set_mlp: kind must be an enum llm_mlp");
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_mlp: rows are active (set the MLP before begin_* / "
+                             "generate / prefill)");
+  LLM_REQUIRE(!d->weights_ready && !d->up_ready,
+              "llm_decoder_set_mlp: weights are loaded (set the MLP before the weights)");
+  d->mlp = kind;
+  d->drop_step_graph();  // the step graph's MLP launches change
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_mlp(const llm_decoder* d) { return d ? d->mlp : -1; }
+
 extern "C" int llm_decoder_set_window(llm_decoder* d, int window) {
   LLM_REQUIRE(d, "llm_decoder_set_window: NULL");
   std::lock_guard<std::mutex> g(d->mu);
@@ -256,6 +273,7 @@ extern "C" kv_cache* llm_decoder_kv(llm_decoder* d) { return d ? d->kv : nullptr
 
 int llm::reset_rows(llm_decoder* d, int batch, int start_pos) {
   LLM_REQUIRE(batch > 0 && batch <= d->maxB, "decoder: batch must be in [1, max_batch]");
+  RET_IF(d->up_check());
   RET_IF(kv_cache_clear(d->kv));
   d->batch = batch;
   if (d->row_group != 1) d->drop_step_graph();  // the captured attention launch used the beam group

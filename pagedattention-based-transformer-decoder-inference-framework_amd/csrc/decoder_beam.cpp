@@ -41,6 +41,7 @@ extern "C" int llm_decoder_beam_search(llm_decoder* d, const int32_t* prompts,
     return fail(LLM_ERR_UNSUPPORTED, "llm_decoder_beam_search: the decoder has a sliding window "
                                      "(llm_decoder_set_window): beam groups take none");
   LLM_REQUIRE(d->weights_ready, "llm_decoder_beam_search: weights not loaded");
+  RET_IF(d->up_check());
   // the step graph's token choice becomes the beam selection for the length
   // of the search (a sampling mode is untouched: beam mode takes precedence)
   struct ModeGuard {

@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "gemm.hpp"
+#include "gemm_gated.hpp"
 #include "gemm_w4.hpp"
 #include "kv_cache_impl.hpp"
 #include "pa_decode.hpp"
@@ -121,6 +122,18 @@ struct llm_decoder {
   // through w4_weight_gemm on the unfused forms; wqkv stays int8
   bool w4 = false;
   int w_keep = 0;  // the GEMM weights fit the Infinity Cache: keep them there (w_keep_for)
+  // llm_decoder_set_mlp: with a gated kind w1 / sw1 / b1 are the gate, w_up /
+  // sw_up / b_up (llm_decoder_set_up_weights; packed like w1, sz_1 per layer)
+  // the up matrix, and layer_post runs csrc/gemm_gated.hip in fc1's place
+  int mlp = LLM_MLP_PLAIN;
+  DevBuf<uint8_t> w_up;
+  DevBuf<float> sw_up, b_up;  // b_up.p NULL: no up bias
+  bool up_ready = false;
+  bool gated() const { return mlp != LLM_MLP_PLAIN; }
+  // LLM_ERR_INVALID for a gated decoder without its up matrix: asked by every
+  // entry that starts rows or runs them
+  int up_check() const;
+  int layer_post_gated(int l, hipStream_t st, const Rows& R);
 
   // KV: fp16 pools, or LLM_FP8 bytes (csrc/fp8.hpp) with one K and one V
   // scale per layer (llm_decoder_set_kv_scales; host copies: the step graph

@@ -201,6 +201,7 @@ int llm_decoder::prefill_run(const int32_t* rows, const int32_t* toks, const int
 // one segment per pass, attended by the single-sequence launch.
 int llm_decoder::prefill(int row, const int32_t* toks, int n, hipStream_t st) {
   LLM_REQUIRE(weights_ready, "prefill: weights not loaded");
+  RET_IF(up_check());
   LLM_REQUIRE(row >= 0 && row < batch, "prefill: row is not active");
   LLM_REQUIRE(n >= 1 && toks, "prefill: need >= 1 token");
   LLM_REQUIRE(h_pos[row] + n < cfg.max_seq_len, "prefill: prompt exceeds max_seq_len");
@@ -214,6 +215,7 @@ int llm_decoder::prefill(int row, const int32_t* toks, int n, hipStream_t st) {
 int llm_decoder::prefill_rows(const int32_t* rows, const int32_t* toks, const int32_t* lens,
                               int nrows, hipStream_t st) {
   LLM_REQUIRE(weights_ready, "prefill_rows: weights not loaded");
+  RET_IF(up_check());
   LLM_REQUIRE(nrows >= 0 && (nrows == 0 || (rows && lens)), "prefill_rows: NULL argument");
   long long total = 0;
   std::vector<char> seen(batch, 0);

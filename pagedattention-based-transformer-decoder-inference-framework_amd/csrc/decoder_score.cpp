@@ -13,6 +13,7 @@
 int llm_decoder::score(const int32_t* toks, const int32_t* lens, int stride, int nseq,
                        float* out) {
   LLM_REQUIRE(weights_ready, "llm_decoder_score: weights not loaded");
+  RET_IF(up_check());
   LLM_REQUIRE(nseq >= 0 && stride >= 1, "llm_decoder_score: bad nseq / stride");
   if (nseq == 0) return LLM_OK;
   LLM_REQUIRE(toks && lens && out, "llm_decoder_score: NULL");

@@ -180,6 +180,7 @@ static int serve_begin(llm_decoder* d, bool prefix_cache) {
   std::lock_guard<std::mutex> g(d->mu);
   LLM_REQUIRE(!d->serving, "llm_decoder_serve_begin: already serving");
   LLM_REQUIRE(d->weights_ready, "llm_decoder_serve_begin: weights not loaded");
+  RET_IF(d->up_check());
   // (beam_mode is set only for the length of llm_decoder_beam_search, which
   // holds the mutex; the test states the entry's contract)
   if (d->beam_mode)

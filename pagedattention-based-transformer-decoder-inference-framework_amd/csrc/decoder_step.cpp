@@ -248,8 +248,75 @@ int llm_decoder::layer_post_w4(int l, hipStream_t st, const Rows& R) {
   return w4_weight_gemm(g, st);
 }
 
+// layer_post with a gated MLP (llm_decoder_set_mlp): o_proj as ever, then
+// LayerNorm 2 as a launch of its own writing packed A (the gated kernel has
+// no prologue; the form layer_post_w4 runs), the gated kernel in fc1's place
+// (csrc/gemm_gated.hip: gate = w1, up = w_up), the row quantiser (INT8; the
+// FP16 kernel writes fc2's packed fp16 input itself) and fc2 unchanged.
+int llm_decoder::layer_post_gated(int l, hipStream_t st, const Rows& R) {
+  const size_t lh = (size_t)l * hid, li = (size_t)l * inter;
+  const bool i8 = wdtype == LLM_I8;
+  WeightGemm g;
+  g.dtype = wdtype;
+  g.a_packed = 1;
+  g.w_keep = w_keep;
+  g.A = R.act;
+  g.M = R.n;
+  g.W_packed = wo.p + sz_o * l; g.N = hid; g.K = hid; g.C = R.x;
+  if (i8) { g.sa = R.sa; g.sw = sw_o.p + lh; }
+  if (quant_prologue(R)) {
+    g.ln_x = R.o;
+    g.ln_quant_only = 1;
+    if (tap_q) { g.act_out = R.act; g.sa_out = R.sa; }
+  }
+  if (!R.oacc) RET_IF(weight_gemm(g, st));  // (fused: the attention wrote x)
+  g.ln_x = nullptr; g.ln_quant_only = 0; g.act_out = nullptr; g.sa_out = nullptr;
+  RET_IF(tap(l, 1, R, hid, st));
+  // LN2 (zeroing x behind it where fc2 runs as two k slices)
+  const bool split_fc2 = fc2_split(R);
+  LnSource src;
+  src.zero_x = split_fc2 ? R.x : nullptr;
+  if (i8)
+    LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, nullptr,
+                                       static_cast<int8_t*>(R.act), R.sa, st, 1,
+                                       split_fc2 ? &src : nullptr));
+  else
+    LLM_HIP_RET(launch_layernorm_f16(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, R.act, st,
+                                     1, nullptr));
+  RET_IF(tap(l, 2, R, hid, st));
+  GatedGemm m;
+  m.dtype = wdtype;
+  m.A = R.act;
+  m.a_packed = 1;
+  m.Wg_packed = w1.p + sz_1 * l;
+  m.Wu_packed = w_up.p + sz_1 * l;
+  m.M = R.n; m.N = inter; m.K = hid;
+  m.b_gate = b1.p + li;
+  m.b_up = b_up.p ? b_up.p + li : nullptr;
+  m.mlp = mlp;
+  m.w_keep = w_keep;
+  if (i8) {
+    m.sa = R.sa; m.sw_gate = sw1.p + li; m.sw_up = sw_up.p + li;
+    m.H = R.h1;
+  } else {
+    m.H16 = R.act2;
+  }
+  RET_IF(gated_gemm(m, st));
+  if (i8)
+    LLM_HIP_RET(launch_quantize_rows(R.h1, R.n, inter, static_cast<int8_t*>(R.act), R.sa, st, 1));
+  else
+    g.A = R.act2;
+  RET_IF(tap(l, 3, R, inter, st));
+  g.W_packed = w2.p + sz_2 * l; g.N = hid; g.K = inter; g.C = R.x;
+  g.bias = b2.p + lh; g.act = LLM_ACT_NONE;
+  if (i8) g.sw = sw2.p + lh;
+  g.ksplit2 = split_fc2 ? 1 : 0;  // (x was zeroed by the LN2 launch)
+  return weight_gemm(g, st);
+}
+
 int llm_decoder::layer_post(int l, hipStream_t st, const Rows& R) {
   if (w4) return layer_post_w4(l, st, R);
+  if (gated()) return layer_post_gated(l, st, R);
   const size_t lh = (size_t)l * hid;
   const bool i8 = wdtype == LLM_I8;
   WeightGemm g;
@@ -423,6 +490,7 @@ int llm_decoder::enqueue_step(hipStream_t st) {
 int llm_decoder::run_step(const int32_t* tokens_host, float* logits_dev, int32_t* next_host,
                           hipStream_t st) {
   LLM_REQUIRE(weights_ready, "decoder: weights not loaded");
+  RET_IF(up_check());
   LLM_REQUIRE(batch > 0, "decoder: no active rows (call generate / begin first)");
   KvCache* k = kv_impl(kv);
   {

@@ -71,8 +71,44 @@ static int upload_common(llm_decoder* d, const uint16_t* emb, const float* ln1_g
 // runs each (profiles/r03/wkeep_ab.txt): C2 (170 MB of weights) +1.7 / +2.1 %
 // kept; C4 (1.2 GB) -2.3 / -2.6 % kept, so nt there.
 static int w_keep_for(const llm_decoder* d) {
-  const size_t bytes = (d->sz_qkv + d->sz_o + d->sz_1 + d->sz_2) * (size_t)d->L;
+  const size_t up = d->gated() ? d->sz_1 : 0;  // (counted before it is loaded: the same size)
+  const size_t bytes = (d->sz_qkv + d->sz_o + d->sz_1 + d->sz_2 + up) * (size_t)d->L;
   return bytes <= (size_t)192 << 20;
+}
+
+static int no_w4_gated(const llm_decoder* d, const char* who) {
+  if (d->gated())
+    return fail(LLM_ERR_UNSUPPORTED, std::string(who) + ": 4-bit weights with a gated MLP are not "
+                                                        "built (the gated kernel reads int8 or fp16)");
+  return LLM_OK;
+}
+
+int llm_decoder::up_check() const {
+  LLM_REQUIRE(!gated() || up_ready, "decoder: the MLP is gated and its up matrix is not loaded "
+                                    "(llm_decoder_set_up_weights)");
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_set_up_weights(llm_decoder* d, const void* w_up, const float* sw_up,
+                                          const float* b_up) {
+  LLM_REQUIRE(d && w_up, "llm_decoder_set_up_weights: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  NOT_SERVING(d, "llm_decoder_set_up_weights");
+  LLM_REQUIRE(d->gated(), "llm_decoder_set_up_weights: the decoder's MLP is plain "
+                          "(llm_decoder_set_mlp first)");
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_up_weights: rows are active");
+  LLM_REQUIRE(d->wdtype != LLM_I8 || sw_up, "llm_decoder_set_up_weights: sw_up is NULL");
+  LLM_HIP_RET(hipStreamSynchronize(d->stream));
+  const int L = d->L, hid = d->hid, inter = d->inter;
+  d->up_ready = false;
+  size_t sz = 0;
+  RET_IF(upload_packed(d->w_up, sz, w_up, L, hid, inter, d->wdtype, "w_up"));
+  if (d->wdtype == LLM_I8) RET_IF(upload(d->sw_up, sw_up, (size_t)L * inter, "sw_up"));
+  if (b_up) RET_IF(upload(d->b_up, b_up, (size_t)L * inter, "b_up"));
+  else RET_IF(d->b_up.alloc(0));
+  d->drop_step_graph();
+  d->up_ready = true;
+  return LLM_OK;
 }
 
 extern "C" int llm_decoder_set_int8_weights(llm_decoder* d, const llm_int8_weights* w) {
@@ -127,6 +163,7 @@ static int upload_w4(DevBuf<uint8_t>& dst, size_t& per_layer, const uint8_t* q, 
 extern "C" int llm_decoder_set_w4_weights(llm_decoder* d, const llm_w4_weights* w) {
   LLM_REQUIRE(d && w, "llm_decoder_set_w4_weights: NULL");
   LLM_REQUIRE(d->wdtype == LLM_I8, "llm_decoder_set_w4_weights: decoder is not INT8");
+  RET_IF(no_w4_gated(d, "llm_decoder_set_w4_weights"));
   LLM_REQUIRE(d->hid % 128 == 0 && d->inter % 128 == 0,
               "llm_decoder_set_w4_weights: hidden_dim and inter_dim must be multiples of 128");
   std::lock_guard<std::mutex> g(d->mu);
@@ -154,6 +191,7 @@ extern "C" int llm_decoder_set_w4_weights(llm_decoder* d, const llm_w4_weights* 
 extern "C" int llm_decoder_set_int8_weights_int4(llm_decoder* d, const llm_int8_weights* w) {
   LLM_REQUIRE(d && w, "llm_decoder_set_int8_weights_int4: NULL");
   LLM_REQUIRE(d->wdtype == LLM_I8, "llm_decoder_set_int8_weights_int4: decoder is not INT8");
+  RET_IF(no_w4_gated(d, "llm_decoder_set_int8_weights_int4"));
   LLM_REQUIRE(d->hid % 128 == 0 && d->inter % 128 == 0,
               "llm_decoder_set_int8_weights_int4: hidden_dim and inter_dim must be multiples "
               "of 128");
@@ -183,7 +221,7 @@ extern "C" int llm_decoder_weight_bits(const llm_decoder* d) {
 
 extern "C" size_t llm_decoder_weight_bytes(const llm_decoder* d) {
   if (!d || !d->weights_ready) return 0;
-  return (d->sz_qkv + d->sz_o + d->sz_1 + d->sz_2) * (size_t)d->L;
+  return (d->sz_qkv + d->sz_o + d->sz_1 + d->sz_2 + (d->up_ready ? d->sz_1 : 0)) * (size_t)d->L;
 }
 
 extern "C" int llm_decoder_expanded_weights(llm_decoder* d, int8_t* wo, int8_t* w1, int8_t* w2) {
@@ -345,8 +383,56 @@ static void quantize_cols(const float* w, int K, int N, int8_t* q, float* inv) {
   }
 }
 
+// Gated MLP: the up matrix of a weight directory, named as w1's files are --
+// layer_i/mlp_up.bin [hid][inter] fp32 (quantised: mlp_up.i8 + mlp_up.scale)
+// and an optional layer_i/mlp_up_bias.bin [inter] fp32 -- read after the main
+// set and handed to llm_decoder_set_up_weights.  A missing matrix is an error.
+static int load_up_dir(llm_decoder* d, const std::string& dir, bool quantised) {
+  const int L = d->L, hid = d->hid, inter = d->inter;
+  const size_t kn = (size_t)hid * inter;
+  std::vector<char> buf;
+  std::vector<float> w, s((size_t)L * inter), b((size_t)L * inter);
+  std::vector<int8_t> q(d->wdtype == LLM_I8 ? kn * L : 0);
+  std::vector<uint16_t> h(d->wdtype == LLM_F16 ? kn * L : 0);
+  bool bias = false;
+  for (int l = 0; l < L; ++l) {
+    const std::string p = dir + "/layer_" + std::to_string(l);
+    if (quantised) {
+      RET_IF(read_file(p + "/mlp_up.i8", buf, kn));
+      std::memcpy(q.data() + kn * l, buf.data(), kn);
+      RET_IF(read_file(p + "/mlp_up.scale", buf, (size_t)inter * 4));
+      std::memcpy(s.data() + (size_t)l * inter, buf.data(), (size_t)inter * 4);
+    } else {
+      w.resize(kn);
+      RET_IF(read_file(p + "/mlp_up.bin", buf, kn * 4));
+      std::memcpy(w.data(), buf.data(), kn * 4);
+      if (d->wdtype == LLM_I8)
+        quantize_cols(w.data(), hid, inter, q.data() + kn * l, s.data() + (size_t)l * inter);
+      else
+        for (size_t i = 0; i < kn; ++i) h[kn * l + i] = f32_to_f16_bits(w[i]);
+    }
+    if (std::ifstream(p + "/mlp_up_bias.bin").good()) {
+      LLM_REQUIRE(bias || l == 0, "decoder weights: mlp_up_bias.bin in some layers only");
+      bias = true;
+      RET_IF(read_file(p + "/mlp_up_bias.bin", buf, (size_t)inter * 4));
+      std::memcpy(b.data() + (size_t)l * inter, buf.data(), (size_t)inter * 4);
+    } else {
+      LLM_REQUIRE(!bias, "decoder weights: mlp_up_bias.bin in some layers only");
+    }
+  }
+  const void* wp = d->wdtype == LLM_I8 ? (const void*)q.data() : (const void*)h.data();
+  return llm_decoder_set_up_weights(d, wp, s.data(), bias ? b.data() : nullptr);
+}
+
+static int load_fp32_weights(llm_decoder* d, const char* dir);
+
 extern "C" int llm_decoder_load_weights(llm_decoder* d, const char* dir) {
   LLM_REQUIRE(d && dir, "llm_decoder_load_weights: NULL");
+  RET_IF(load_fp32_weights(d, dir));
+  return d->gated() ? load_up_dir(d, dir, false) : LLM_OK;
+}
+
+static int load_fp32_weights(llm_decoder* d, const char* dir) {
   const int L = d->L, hid = d->hid, inter = d->inter, V = d->V;
   Fp32Model m;
   RET_IF(load_fp32_dir(dir, L, hid, inter, V, m));
@@ -395,6 +481,9 @@ extern "C" int llm_quantize_weights(const char* fp32_dir, const char* int8_dir, 
   LLM_REQUIRE(fp32_dir && int8_dir && num_layers > 0 && hidden_dim > 0 && vocab_size > 0,
               "llm_quantize_weights: bad arguments");
   const int L = num_layers, hid = hidden_dim, inter = inter_dim > 0 ? inter_dim : 4 * hidden_dim;
+  if (std::ifstream(std::string(fp32_dir) + "/layer_0/mlp_up.bin").good())
+    return fail(LLM_ERR_UNSUPPORTED, "llm_quantize_weights: the directory holds a gated MLP's up "
+                                     "matrix (mlp_up.bin), which this quantiser does not write");
   Fp32Model m;
   RET_IF(load_fp32_dir(fp32_dir, L, hid, inter, vocab_size, m));
   const std::string out = int8_dir;
@@ -470,7 +559,8 @@ static int load_int8_dir(llm_decoder* d, const char* dir, bool int4) {
   llm_int8_weights w{emb.data(), g1.data(), be1.data(), g2.data(), be2.data(), qqkv.data(),
                      sqkv.data(), qo.data(), so.data(), q1.data(), s1.data(), b1.data(),
                      q2.data(), s2.data(), b2.data()};
-  return int4 ? llm_decoder_set_int8_weights_int4(d, &w) : llm_decoder_set_int8_weights(d, &w);
+  RET_IF(int4 ? llm_decoder_set_int8_weights_int4(d, &w) : llm_decoder_set_int8_weights(d, &w));
+  return d->gated() ? load_up_dir(d, root, true) : LLM_OK;
 }
 
 extern "C" int llm_decoder_load_quantized_weights(llm_decoder* d, const char* dir) {

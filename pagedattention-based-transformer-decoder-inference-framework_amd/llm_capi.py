@@ -23,6 +23,7 @@ TUNE_LIB_PATH = HERE / "libllm_decoder_hip_tune.so"  # `make tune`: A/B hooks, n
  LLM_ERR_RANGE) = range(7)
 LLM_F16, LLM_I8, LLM_F32, LLM_BF16, LLM_FP8, LLM_I4 = 0, 1, 2, 3, 4, 5
 LLM_ACT_NONE, LLM_ACT_RELU, LLM_ACT_GELU = 0, 1, 2
+LLM_MLP_PLAIN, LLM_MLP_GATED_SILU, LLM_MLP_GATED_GELU = 0, 1, 2
 LLM_EVICT_NONE, LLM_EVICT_LRU = 0, 1
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
@@ -216,6 +217,14 @@ _SIGS = {
     "gemm_pack_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "i8_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                         c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    # gated MLP (csrc/gemm_gated.hip)
+    "i8_gemm_gated": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int] * 3 +
+                      [c_void_p] * 5 + [c_int, c_void_p]),
+    "f16_gemm_gated": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] * 3 +
+                       [c_void_p] * 2 + [c_int, c_void_p]),
+    "llm_decoder_set_mlp": (c_int, [c_void_p, c_int]),
+    "llm_decoder_mlp": (c_int, [c_void_p]),
+    "llm_decoder_set_up_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     # INT4 weights (csrc/gemm_w4.hip, csrc/w4_quant.cpp)
     "w4_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "w4_expand": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -795,6 +804,37 @@ def i8_gemm(A, W_packed, N, *, sa=None, sw=None, bias=None, act=0, want_acc=True
     check(lib.i8_gemm(ptr(A), A.stride(0), ptr(W_packed), ptr(acc), ptr(C), M, N, K, ptr(sa),
                       ptr(sw), ptr(bias), act, stream_ptr(stream)))
     return acc, C
+
+
+def gemm_gated(A, Wg_packed, Wu_packed, N, *, M=None, K=None, sa=None, sw_gate=None, sw_up=None,
+               b_gate=None, b_up=None, mlp=LLM_MLP_GATED_SILU, want_acc=True, want_h16=True,
+               stream=None):
+    """i8_gemm_gated (int8 A) / f16_gemm_gated (fp16 A) over device tensors.  A:
+    [M][K] row-major (any row stride), or with M and K given a flat tensor in
+    packed-A order.  Returns (acc_gate, acc_up, H, H16): the int32 sums (None for
+    fp16 or without want_acc), H fp32 [M][N], and H16 as a flat fp16 tensor in
+    packed-A order with ceil(N/32) k-steps per row tile (zero where unwritten)."""
+    import torch
+    lib = load()
+    packed = M is not None
+    if not packed:
+        M, K = A.shape
+    i8 = A.dtype == torch.int8
+    dev = A.device
+    H = torch.empty((M, N), dtype=torch.float32, device=dev)
+    H16 = (torch.zeros((M + 15) // 16 * ((N + 31) // 32) * 512, dtype=torch.float16, device=dev)
+           if want_h16 else None)
+    lda, pk = (0 if packed else A.stride(0)), (1 if packed else 0)
+    if i8:
+        ag = torch.empty((M, N), dtype=torch.int32, device=dev) if want_acc else None
+        au = torch.empty((M, N), dtype=torch.int32, device=dev) if want_acc else None
+        check(lib.i8_gemm_gated(ptr(A), lda, pk, ptr(Wg_packed), ptr(Wu_packed), ptr(ag), ptr(au),
+                                ptr(H), ptr(H16), M, N, K, ptr(sa), ptr(sw_gate), ptr(sw_up),
+                                ptr(b_gate), ptr(b_up), mlp, stream_ptr(stream)))
+        return ag, au, H, H16
+    check(lib.f16_gemm_gated(ptr(A), lda, pk, ptr(Wg_packed), ptr(Wu_packed), ptr(H), ptr(H16),
+                             M, N, K, ptr(b_gate), ptr(b_up), mlp, stream_ptr(stream)))
+    return None, None, H, H16
 
 
 def w4_quantize(W8):
