@@ -53,6 +53,9 @@ enum llm_act { LLM_ACT_NONE = 0, LLM_ACT_RELU = 1, LLM_ACT_GELU = 2 };
  * GEMMs: plain fc2(relu(fc1(x) + b1)) + b2, or gated
  * fc2(act(gate(x)) * up(x)) + b2 with act = SiLU (SwiGLU) or erf-GELU (GeGLU). */
 enum llm_mlp { LLM_MLP_PLAIN = 0, LLM_MLP_GATED_SILU = 1, LLM_MLP_GATED_GELU = 2 };
+/* The decoder's normalisation (llm_decoder_set_norm): LayerNorm, or RMSNorm
+ * as defined at rmsnorm_quant. */
+enum llm_norm { LLM_NORM_LAYER = 0, LLM_NORM_RMS = 1 };
 
 const char* llm_last_error(void);
 int llm_abi_version(void);
@@ -389,6 +392,24 @@ int i8_gemm_gated(const int8_t* A, int lda, int a_packed, const void* Wg_packed,
 int f16_gemm_gated(const void* A, int lda, int a_packed, const void* Wg_packed,
                    const void* Wu_packed, float* H, void* H16, int M, int N, int K,
                    const float* b_gate, const float* b_up, int mlp, void* stream);
+/* The gated launch with RMSNorm (rmsnorm_quant's definition) as its prologue:
+ * A = RMSNorm(x) of fp32 rows x [M][K], computed by every workgroup for its
+ * rows into LDS (I8: quantised per row, the row scales taking sa's place) and
+ * bit-identical to rmsnorm_quant's image and scales.  a_out / sa_out (optional)
+ * receive that image in A-fragment order (ceil(M/16) whole row tiles) and the
+ * I8 row scales.  Everything else as i8_gemm_gated / f16_gemm_gated.  Shapes the
+ * prologue does not take (K > 2048, M > 64, an LDS image past 160 KiB, or too
+ * many bytes of fp32 rows per workgroup: DESIGN, "RMSNorm") return
+ * LLM_ERR_UNSUPPORTED:
+ * rmsnorm_quant followed by the gated launch serves them. */
+int i8_gemm_gated_rms(const float* x, const float* gamma, float eps, const void* Wg_packed,
+                      const void* Wu_packed, int32_t* acc_gate, int32_t* acc_up, float* H,
+                      void* H16, int M, int N, int K, const float* sw_gate, const float* sw_up,
+                      const float* b_gate, const float* b_up, int mlp, int8_t* a_out,
+                      float* sa_out, void* stream);
+int f16_gemm_gated_rms(const float* x, const float* gamma, float eps, const void* Wg_packed,
+                       const void* Wu_packed, float* H, void* H16, int M, int N, int K,
+                       const float* b_gate, const float* b_up, int mlp, void* a_out, void* stream);
 
 /* INT4 weights (LLM_I4): a two-level integer format.  For W [K][N] with
  * K % 128 == 0, N % 16 == 0, K < 131072:
@@ -569,6 +590,36 @@ int quantize_rows(const float* x, int rows, int cols, int8_t* q, float* inv_scal
  * (q/inv_scale may be NULL: then only `out` fp32 is written; out may be NULL). */
 int layernorm_quant(const float* x, int rows, int cols, const float* gamma, const float* beta,
                     float eps, float* out, int8_t* q, float* inv_scale, void* stream);
+
+/* RMSNorm.  One definition, obeyed by the row launch (rmsnorm_quant), the
+ * weight GEMM's prologue (i8_gemm_rms / f16_gemm_rms), the gated kernel's
+ * prologue (i8_gemm_gated_rms / f16_gemm_gated_rms) and the decoder under
+ * llm_decoder_set_norm(LLM_NORM_RMS); fp32 rows of K elements:
+ *   ms      = (sum_i x[i]^2) / K     fmaf accumulation, in the LayerNorm forms'
+ *                                    reduction order (per-thread partials, four
+ *                                    wave sums, their fixed combination)
+ *   inv_rms = (float)(1.0 / (double)sqrtf(ms + eps))
+ *   y[i]    = (x[i] * inv_rms) * gamma[i]    each product rounded once, not
+ *                                            contracted; there is no beta
+ * The int8 image and the row scale are layernorm_quant's: scale = 127 /
+ * (absmax + 1e-6), q = clamp(round(y * scale)), inv_scale = 1 / scale.  Every
+ * form gives the same bits for a row, whatever the batch size.  Gemma's
+ * (1 + gamma) convention: add 1 to gamma.  eps > 0.
+ * rmsnorm_quant: the column and NULL rules of layernorm_quant. */
+int rmsnorm_quant(const float* x, int rows, int cols, const float* gamma, float eps, float* out,
+                  int8_t* q, float* inv_scale, void* stream);
+/* i8_gemm / f16_gemm over A = RMSNorm(x), the norm running as the GEMM's
+ * prologue (x fp32 [M][K] row-major; W_packed from gemm_pack_weights; C fp32
+ * [M][N]).  I8: C = act(acc * sa[m] * sw[n] + bias[n]) with the prologue's row
+ * scales as sa.  a_out / sa_out (optional): the image in A-fragment order and
+ * the I8 row scales, bit-identical to rmsnorm_quant's.  Rows the prologue does
+ * not take (K > 2048, K * element size % 256 != 0, more than 64 KiB of fp32
+ * per 16 / 32 / 64-row block) return LLM_ERR_UNSUPPORTED. */
+int i8_gemm_rms(const float* x, const float* gamma, float eps, const void* W_packed, float* C,
+                int M, int N, int K, const float* sw, const float* bias, int act, int8_t* a_out,
+                float* sa_out, void* stream);
+int f16_gemm_rms(const float* x, const float* gamma, float eps, const void* W_packed, float* C,
+                 int M, int N, int K, const float* bias, int act, void* a_out, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* KV cache: page pools + page table (kv_cache/page_table.hpp:5-37,          */
@@ -799,6 +850,20 @@ int llm_decoder_window(const llm_decoder* d);
 int llm_decoder_set_mlp(llm_decoder* d, int kind);
 /* The decoder's enum llm_mlp, -1 for NULL. */
 int llm_decoder_mlp(const llm_decoder* d);
+/* The decoder's normalisation (enum llm_norm; LLM_NORM_LAYER with eps 1e-5 by
+ * default) and its eps, for either kind.  With LLM_NORM_RMS both norms of every layer are RMSNorm
+ * (rmsnorm_quant's definition) with this eps: norm 1 as the qkv projection's
+ * prologue on decode rows and a launch on prompt chunks; norm 2 as fc1's
+ * prologue (plain MLP), the gated kernel's prologue where it takes the rows
+ * (else a launch before the gated launch), or a launch (4-bit weights).
+ * ln1_b / ln2_b of the weight sets may then be NULL and are ignored; the
+ * ln*.bin files of a weight directory may hold gamma alone.  There is no final
+ * norm before the LM head.  Allowed only before any weights are set and while
+ * no rows are active (LLM_ERR_INVALID otherwise, as for an unknown kind or
+ * eps <= 0). */
+int llm_decoder_set_norm(llm_decoder* d, int kind, float eps);
+/* The decoder's enum llm_norm, -1 for NULL. */
+int llm_decoder_norm(const llm_decoder* d);
 /* The up matrix of a gated MLP, host arrays: w_up [L][hid][inter] int8 with
  * sw_up [L][inter] (INT8 decoder) or fp16 with sw_up ignored (FP16 decoder);
  * b_up [L][inter] fp32 or NULL (no bias).  LLM_ERR_INVALID on a plain-MLP

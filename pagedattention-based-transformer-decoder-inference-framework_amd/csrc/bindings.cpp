@@ -111,8 +111,12 @@ class Decoder {
     const size_t L = cfg_.num_layers, hid = cfg_.hidden_dim, inter = cfg_.inter_dim,
                  V = cfg_.vocab_size;
     auto emb = arr<uint16_t>(w, "emb", V * hid);
-    auto ln1_g = arr<float>(w, "ln1_g", L * hid), ln1_b = arr<float>(w, "ln1_b", L * hid);
-    auto ln2_g = arr<float>(w, "ln2_g", L * hid), ln2_b = arr<float>(w, "ln2_b", L * hid);
+    auto ln1_g = arr<float>(w, "ln1_g", L * hid), ln2_g = arr<float>(w, "ln2_g", L * hid);
+    // RMSNorm (set_norm("rms")) has no beta: the keys may be absent
+    py::array_t<float, py::array::c_style | py::array::forcecast> ln1_b, ln2_b;
+    const bool beta = llm_decoder_norm(d_) != LLM_NORM_RMS;
+    if (beta || w.contains("ln1_b")) ln1_b = arr<float>(w, "ln1_b", L * hid);
+    if (beta || w.contains("ln2_b")) ln2_b = arr<float>(w, "ln2_b", L * hid);
     auto b1 = arr<float>(w, "b1", L * inter), b2 = arr<float>(w, "b2", L * hid);
     if (cfg_.weight_dtype == LLM_I8) {
       auto wqkv = arr<int8_t>(w, "wqkv", L * hid * 3 * hid), wo = arr<int8_t>(w, "wo", L * hid * hid);
@@ -158,6 +162,13 @@ class Decoder {
     if (k < 0) throw std::invalid_argument("set_mlp: 'plain', 'gated_silu' or 'gated_gelu'");
     check(llm_decoder_set_mlp(d_, k));
   }
+  // llm_decoder_set_norm: "layer" or "rms"
+  void set_norm(const std::string& kind, float eps) {
+    const int k = kind == "layer" ? LLM_NORM_LAYER : kind == "rms" ? LLM_NORM_RMS : -1;
+    if (k < 0) throw std::invalid_argument("set_norm: 'layer' or 'rms'");
+    check(llm_decoder_set_norm(d_, k, eps));
+  }
+  std::string norm() const { return llm_decoder_norm(d_) == LLM_NORM_RMS ? "rms" : "layer"; }
   std::string mlp() const {
     const int k = llm_decoder_mlp(d_);
     return k == LLM_MLP_GATED_SILU ? "gated_silu" : k == LLM_MLP_GATED_GELU ? "gated_gelu" : "plain";
@@ -934,6 +945,8 @@ PYBIND11_MODULE(llm_decoder, m) {
         .def_property_readonly("rope", &Decoder::rope)
         .def("set_mlp", &Decoder::set_mlp, py::arg("kind"))
         .def_property_readonly("mlp", &Decoder::mlp)
+        .def("set_norm", &Decoder::set_norm, py::arg("kind"), py::arg("eps") = 1e-5f)
+        .def("norm", &Decoder::norm)
         .def("set_window", &Decoder::set_window, py::arg("window"))
         .def_property_readonly("window", &Decoder::window)
         .def("set_shared_attention", &Decoder::set_shared_attention, py::arg("min_pages") = -1)

@@ -211,6 +211,25 @@ extern "C" int llm_decoder_set_mlp(llm_decoder* d, int kind) {
 
 extern "C" int llm_decoder_mlp(const llm_decoder* d) { return d ? d->mlp : -1; }
 
+extern "C" int llm_decoder_set_norm(llm_decoder* d, int kind, float eps) {
+  LLM_REQUIRE(d, "llm_decoder_set_norm: NULL");
+  std::lock_guard<std::mutex> g(d->mu);
+  NOT_SERVING(d, "llm_decoder_set_norm");
+  LLM_REQUIRE(kind == LLM_NORM_LAYER || kind == LLM_NORM_RMS,
+              "llm_decoder_set_norm: kind must be an enum llm_norm");
+  LLM_REQUIRE(std::isfinite(eps) && eps > 0.f, "llm_decoder_set_norm: eps must be finite and > 0");
+  LLM_REQUIRE(d->batch == 0, "llm_decoder_set_norm: rows are active (set the norm before begin_* / "
+                             "generate / prefill)");
+  LLM_REQUIRE(!d->weights_ready && !d->up_ready,
+              "llm_decoder_set_norm: weights are loaded (set the norm before the weights)");
+  d->norm = kind;
+  d->norm_eps = eps;
+  d->drop_step_graph();  // the step graph's norm launches and prologues change
+  return LLM_OK;
+}
+
+extern "C" int llm_decoder_norm(const llm_decoder* d) { return d ? d->norm : -1; }
+
 extern "C" int llm_decoder_set_window(llm_decoder* d, int window) {
   LLM_REQUIRE(d, "llm_decoder_set_window: NULL");
   std::lock_guard<std::mutex> g(d->mu);

@@ -134,6 +134,13 @@ struct llm_decoder {
   // entry that starts rows or runs them
   int up_check() const;
   int layer_post_gated(int l, hipStream_t st, const Rows& R);
+  // llm_decoder_set_norm: both norms of every layer (enum llm_norm) and their
+  // eps; under LLM_NORM_RMS ln1_b / ln2_b are not uploaded and never read
+  int norm = LLM_NORM_LAYER;
+  float norm_eps = 1e-5f;
+  bool rms() const { return norm == LLM_NORM_RMS; }
+  int norm_launch(const Rows& R, const float* gamma, const float* beta, hipStream_t st,
+                  const LnSource* pp);
 
   // KV: fp16 pools, or LLM_FP8 bytes (csrc/fp8.hpp) with one K and one V
   // scale per layer (llm_decoder_set_kv_scales; host copies: the step graph

@@ -52,9 +52,27 @@ int llm_decoder::layer_pre(int l, hipStream_t st, const Rows& R, const LnSource*
   g.C = R.q; g.c_cols = hid; g.c_ld = hid;  // q only: K and V go straight into the pages
   g.kv = &app;
   if (wdtype == LLM_I8) g.sa = R.sa, g.sw = sw_qkv.p + (size_t)l * 3 * hid;
-  RET_IF(layer_norm_into(g, R, ln1_g.p + lh, ln1_b.p + lh, st, nullptr, emb));
+  RET_IF(layer_norm_into(g, R, ln1_g.p + lh, rms() ? nullptr : ln1_b.p + lh, st, nullptr, emb));
   RET_IF(weight_gemm(g, st));
   return tap(l, 0, R, hid, st);
+}
+
+// The norm (llm_decoder_set_norm) of R.x, or of the rows pp names, as a launch
+// of its own writing the packed A the next GEMM reads: int8 + row scales, or
+// fp16.  beta is unused under RMSNorm.
+int llm_decoder::norm_launch(const Rows& R, const float* gamma, const float* beta, hipStream_t st,
+                             const LnSource* pp) {
+  const bool i8 = wdtype == LLM_I8;
+  if (rms())
+    LLM_HIP_RET(launch_rmsnorm(R.x, R.n, hid, gamma, norm_eps, nullptr,
+                               i8 ? static_cast<int8_t*>(R.act) : nullptr, i8 ? R.sa : nullptr,
+                               i8 ? nullptr : R.act, st, 1, pp));
+  else if (i8)
+    LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, gamma, beta, norm_eps, nullptr,
+                                       static_cast<int8_t*>(R.act), R.sa, st, 1, pp));
+  else
+    LLM_HIP_RET(launch_layernorm_f16(R.x, R.n, hid, gamma, beta, norm_eps, R.act, st, 1, pp));
+  return LLM_OK;
 }
 
 // LN(x) as the GEMM's A: fused into the GEMM as its LayerNorm prologue when
@@ -68,18 +86,12 @@ int llm_decoder::layer_norm_into(WeightGemm& g, const Rows& R, const float* gamm
   LnSource src = emb ? *emb : LnSource{};
   src.zero_x = zero_x;  // (the LayerNorm launch only: the caller checks fc2_split)
   if (!R.is_prefill() && ln_fusable(wdtype, R.n, hid)) {
-    g.ln_x = R.x; g.ln_g = gamma; g.ln_b = beta; g.ln_eps = 1e-5f;
+    g.ln_x = R.x; g.ln_g = gamma; g.ln_b = beta; g.ln_eps = norm_eps; g.ln_norm = norm;
     g.ln_emb = src.emb; g.ln_tok = src.tok; g.ln_V = src.V;
     if (tap_q) { g.act_out = R.act; g.sa_out = R.sa; }  // the taps read A and the scales back
     return LLM_OK;
   }
-  const LnSource* pp = src.emb || src.zero_x ? &src : nullptr;
-  if (wdtype == LLM_I8)
-    LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, gamma, beta, 1e-5f, nullptr,
-                                       static_cast<int8_t*>(R.act), R.sa, st, 1, pp));
-  else
-    LLM_HIP_RET(launch_layernorm_f16(R.x, R.n, hid, gamma, beta, 1e-5f, R.act, st, 1, pp));
-  return LLM_OK;
+  return norm_launch(R, gamma, beta, st, src.emb || src.zero_x ? &src : nullptr);
 }
 
 // INT8 decode rows whose o_proj can quantise its own input (gemm.hip
@@ -232,8 +244,7 @@ int llm_decoder::layer_post_w4(int l, hipStream_t st, const Rows& R) {
   RET_IF(w4_weight_gemm(g, st));
   RET_IF(tap(l, 1, R, hid, st));
   // LN2 -> mlp_fc1 (+b1, ReLU)
-  LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, nullptr,
-                                     act, R.sa, st, 1, nullptr));
+  RET_IF(norm_launch(R, ln2_g.p + lh, rms() ? nullptr : ln2_b.p + lh, st, nullptr));
   g.W_packed = w1.p + sz_1 * l; g.N = inter; g.K = hid; g.C = R.h1;
   g.sw = sw1.p + (size_t)l * inter;
   g.bias = b1.p + (size_t)l * inter; g.act = LLM_ACT_RELU;
@@ -273,19 +284,23 @@ int llm_decoder::layer_post_gated(int l, hipStream_t st, const Rows& R) {
   g.ln_x = nullptr; g.ln_quant_only = 0; g.act_out = nullptr; g.sa_out = nullptr;
   RET_IF(tap(l, 1, R, hid, st));
   // LN2 (zeroing x behind it where fc2 runs as two k slices)
-  const bool split_fc2 = fc2_split(R);
+  // RMSNorm on decode rows the gated kernel takes (gated_rms_fusable): norm 2
+  // is that kernel's prologue, no launch of its own.  Nothing then zeroes x
+  // behind the norm (every workgroup reads the rows), so fc2 runs unsplit.
+  const bool fuse = rms() && !R.is_prefill() && gated_rms_fusable(wdtype, R.n, inter, hid);
+  const bool split_fc2 = !fuse && fc2_split(R);
   LnSource src;
   src.zero_x = split_fc2 ? R.x : nullptr;
-  if (i8)
-    LLM_HIP_RET(launch_layernorm_quant(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, nullptr,
-                                       static_cast<int8_t*>(R.act), R.sa, st, 1,
-                                       split_fc2 ? &src : nullptr));
-  else
-    LLM_HIP_RET(launch_layernorm_f16(R.x, R.n, hid, ln2_g.p + lh, ln2_b.p + lh, 1e-5f, R.act, st,
-                                     1, nullptr));
-  RET_IF(tap(l, 2, R, hid, st));
   GatedGemm m;
   m.dtype = wdtype;
+  if (fuse) {
+    m.ln_x = R.x; m.ln_g = ln2_g.p + lh; m.ln_eps = norm_eps;
+    if (tap_q) { m.act_out = R.act; m.sa_out = R.sa; }  // the taps read A and the scales back
+  } else {
+    RET_IF(norm_launch(R, ln2_g.p + lh, rms() ? nullptr : ln2_b.p + lh, st,
+                       i8 && split_fc2 ? &src : nullptr));
+    RET_IF(tap(l, 2, R, hid, st));
+  }
   m.A = R.act;
   m.a_packed = 1;
   m.Wg_packed = w1.p + sz_1 * l;
@@ -302,6 +317,7 @@ int llm_decoder::layer_post_gated(int l, hipStream_t st, const Rows& R) {
     m.H16 = R.act2;
   }
   RET_IF(gated_gemm(m, st));
+  if (fuse) RET_IF(tap(l, 2, R, hid, st));
   if (i8)
     LLM_HIP_RET(launch_quantize_rows(R.h1, R.n, inter, static_cast<int8_t*>(R.act), R.sa, st, 1));
   else
@@ -340,7 +356,8 @@ int llm_decoder::layer_post(int l, hipStream_t st, const Rows& R) {
   RET_IF(tap(l, 1, R, hid, st));
   // LN2 -> mlp_fc1 (+b1, ReLU)
   const bool split_fc2 = fc2_split(R);
-  RET_IF(layer_norm_into(g, R, ln2_g.p + lh, ln2_b.p + lh, st, split_fc2 ? R.x : nullptr));
+  RET_IF(layer_norm_into(g, R, ln2_g.p + lh, rms() ? nullptr : ln2_b.p + lh, st,
+                         split_fc2 ? R.x : nullptr));
   g.W_packed = w1.p + sz_1 * l; g.N = inter; g.K = hid;
   g.bias = b1.p + (size_t)l * inter; g.act = LLM_ACT_RELU;
   if (i8) {

@@ -57,9 +57,11 @@ static int upload_common(llm_decoder* d, const uint16_t* emb, const float* ln1_g
   LLM_HIP_RET(launch_lm_pack(d->emb.p, d->emb_packed.p, d->V, d->hid, nullptr));
   LLM_HIP_RET(hipDeviceSynchronize());
   RET_IF(upload(d->ln1_g, ln1_g, Lh, "ln1_g"));
-  RET_IF(upload(d->ln1_b, ln1_b, Lh, "ln1_b"));
   RET_IF(upload(d->ln2_g, ln2_g, Lh, "ln2_g"));
-  RET_IF(upload(d->ln2_b, ln2_b, Lh, "ln2_b"));
+  if (!d->rms()) {  // (RMSNorm has no beta: the pointers may be NULL and are not read)
+    RET_IF(upload(d->ln1_b, ln1_b, Lh, "ln1_b"));
+    RET_IF(upload(d->ln2_b, ln2_b, Lh, "ln2_b"));
+  }
   return LLM_OK;
 }
 
@@ -318,7 +320,22 @@ struct Fp32Model {
   std::vector<float> emb, ln1, ln2, wqkv, wo, w1, w2, b1, b2;  // ln: [L][2][hid]
 };
 
-static int load_fp32_dir(const std::string& dir, int L, int hid, int inter, int V, Fp32Model& m) {
+// A layer's norm file: gamma + beta [2][hid] fp32, or gamma alone [hid] where
+// gamma_only is allowed (an RMSNorm decoder; beta then reads as zeros).
+static int read_ln(const std::string& path, int hid, bool gamma_only, float* gb) {
+  std::vector<char> buf;
+  RET_IF(read_file(path, buf, 0));
+  const size_t full = (size_t)2 * hid * 4;
+  if (buf.size() != full && !(gamma_only && buf.size() == full / 2))
+    return fail(LLM_ERR_IO, path + ": expected " + std::to_string(full) + " bytes, found " +
+                                std::to_string(buf.size()));
+  std::memset(gb, 0, full);
+  std::memcpy(gb, buf.data(), buf.size());
+  return LLM_OK;
+}
+
+static int load_fp32_dir(const std::string& dir, int L, int hid, int inter, int V, Fp32Model& m,
+                         bool gamma_only = false) {
   std::vector<char> buf;
   auto rd = [&](const std::string& p, size_t n, float* dst) -> int {
     RET_IF(read_file(p, buf, n * 4));
@@ -334,8 +351,8 @@ static int load_fp32_dir(const std::string& dir, int L, int hid, int inter, int 
   std::vector<float> tmp((size_t)hid * hid), bias(inter + hid);
   for (int l = 0; l < L; ++l) {
     const std::string p = dir + "/layer_" + std::to_string(l);
-    RET_IF(rd(p + "/ln1.bin", 2 * hid, m.ln1.data() + (size_t)l * 2 * hid));
-    RET_IF(rd(p + "/ln2.bin", 2 * hid, m.ln2.data() + (size_t)l * 2 * hid));
+    RET_IF(read_ln(p + "/ln1.bin", hid, gamma_only, m.ln1.data() + (size_t)l * 2 * hid));
+    RET_IF(read_ln(p + "/ln2.bin", hid, gamma_only, m.ln2.data() + (size_t)l * 2 * hid));
     const char* names[3] = {"/attn_wq.bin", "/attn_wk.bin", "/attn_wv.bin"};
     for (int j = 0; j < 3; ++j) {  // fuse q|k|v column blocks: Wqkv[k][j*hid + n]
       RET_IF(rd(p + names[j], (size_t)hid * hid, tmp.data()));
@@ -435,7 +452,7 @@ extern "C" int llm_decoder_load_weights(llm_decoder* d, const char* dir) {
 static int load_fp32_weights(llm_decoder* d, const char* dir) {
   const int L = d->L, hid = d->hid, inter = d->inter, V = d->V;
   Fp32Model m;
-  RET_IF(load_fp32_dir(dir, L, hid, inter, V, m));
+  RET_IF(load_fp32_dir(dir, L, hid, inter, V, m, d->rms()));
   std::vector<float> g1, be1, g2, be2;
   split_ln(m.ln1, L, hid, g1, be1);
   split_ln(m.ln2, L, hid, g2, be2);
@@ -535,12 +552,13 @@ static int load_int8_dir(llm_decoder* d, const char* dir, bool int4) {
       s2((size_t)L * hid), b1((size_t)L * inter), b2((size_t)L * hid);
   for (int l = 0; l < L; ++l) {
     const std::string p = root + "/layer_" + std::to_string(l);
-    RET_IF(read_file(p + "/ln1.bin", buf, (size_t)2 * hid * 4));
-    std::memcpy(g1.data() + (size_t)l * hid, buf.data(), hid * 4);
-    std::memcpy(be1.data() + (size_t)l * hid, buf.data() + hid * 4, hid * 4);
-    RET_IF(read_file(p + "/ln2.bin", buf, (size_t)2 * hid * 4));
-    std::memcpy(g2.data() + (size_t)l * hid, buf.data(), hid * 4);
-    std::memcpy(be2.data() + (size_t)l * hid, buf.data() + hid * 4, hid * 4);
+    std::vector<float> gb((size_t)2 * hid);
+    RET_IF(read_ln(p + "/ln1.bin", hid, d->rms(), gb.data()));
+    std::memcpy(g1.data() + (size_t)l * hid, gb.data(), hid * 4);
+    std::memcpy(be1.data() + (size_t)l * hid, gb.data() + hid, hid * 4);
+    RET_IF(read_ln(p + "/ln2.bin", hid, d->rms(), gb.data()));
+    std::memcpy(g2.data() + (size_t)l * hid, gb.data(), hid * 4);
+    std::memcpy(be2.data() + (size_t)l * hid, gb.data() + hid, hid * 4);
     struct { const char* name; int8_t* q; float* s; int K, N; } mats[4] = {
         {"attn_wqkv", qqkv.data() + (size_t)l * hid * 3 * hid, sqkv.data() + (size_t)l * 3 * hid, hid, 3 * hid},
         {"attn_wo", qo.data() + (size_t)l * hid * hid, so.data() + (size_t)l * hid, hid, hid},

@@ -80,6 +80,48 @@ extern "C" int f16_gemm(const void* A, int lda, const void* W_packed, float* C, 
   return LLM_OK;
 }
 
+// i8_gemm_rms / f16_gemm_rms: one weight GEMM with the RMSNorm prologue from
+// fp32 rows (weight_gemm's form, with the checks of a public entry).
+static int gemm_rms(int dtype, const char* who_c, const float* x, const float* gamma, float eps,
+                    const void* W_packed, float* C, int M, int N, int K, const float* sw,
+                    const float* bias, int act, void* a_out, float* sa_out, void* stream) {
+  const std::string who = who_c;
+  const int kstep = dtype == LLM_I8 ? 64 : 32;
+  LLM_REQUIRE(M >= 0 && N > 0 && K > 0, who + ": bad M/N/K");
+  LLM_REQUIRE(eps > 0.f, who + ": eps must be > 0");
+  if (M == 0) return LLM_OK;
+  LLM_REQUIRE(x && gamma && W_packed && C, who + ": NULL operand");
+  LLM_REQUIRE(K % kstep == 0, who + ": K must be a multiple of " + std::to_string(kstep));
+  LLM_REQUIRE(N % 16 == 0, who + ": N must be a multiple of 16");
+  LLM_REQUIRE(act >= 0 && act <= 2, who + ": bad activation");
+  if (!ln_fusable(dtype, M, K))
+    return fail(LLM_ERR_UNSUPPORTED, who + ": these rows' A image does not take the prologue "
+                                           "(ln_fusable: rmsnorm_quant, then the plain GEMM)");
+  WeightGemm g;
+  g.dtype = dtype;
+  g.W_packed = W_packed;
+  g.M = M; g.N = N; g.K = K;
+  g.sw = sw; g.bias = bias; g.act = act;
+  g.C = C;
+  g.a_packed = 1;
+  g.ln_x = x; g.ln_g = gamma; g.ln_eps = eps; g.ln_norm = LLM_NORM_RMS;
+  g.act_out = a_out; g.sa_out = sa_out;
+  return weight_gemm(g, as_stream(stream));
+}
+
+extern "C" int i8_gemm_rms(const float* x, const float* gamma, float eps, const void* W_packed,
+                           float* C, int M, int N, int K, const float* sw, const float* bias,
+                           int act, int8_t* a_out, float* sa_out, void* stream) {
+  return gemm_rms(LLM_I8, "i8_gemm_rms", x, gamma, eps, W_packed, C, M, N, K, sw, bias, act, a_out,
+                  sa_out, stream);
+}
+
+extern "C" int f16_gemm_rms(const float* x, const float* gamma, float eps, const void* W_packed,
+                            float* C, int M, int N, int K, const float* bias, int act, void* a_out,
+                            void* stream) {
+  return gemm_rms(LLM_F16, "f16_gemm_rms", x, gamma, eps, W_packed, C, M, N, K, nullptr, bias, act,
+                  a_out, nullptr, stream);
+}
 
 // The prologue pays off only while the fp32 rows every workgroup reads stay
 // small: all workgroups read all of them, and a CU takes in L2-resident data
@@ -112,7 +154,8 @@ int llm::weight_gemm(const WeightGemm& g, hipStream_t st) {
   LLM_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && (g.A || g.ln_x) && g.W_packed,
               "weight_gemm: bad arguments");
   LLM_REQUIRE(!g.ln_x || (g.ln_quant_only ? g.dtype == LLM_I8 && quant_prologue_ok(g.M, g.N, g.K)
-                                           : g.ln_g && g.ln_b && ln_fusable(g.dtype, g.M, g.K)),
+                                           : g.ln_g && (g.ln_b || g.ln_norm == LLM_NORM_RMS) &&
+                                                 ln_fusable(g.dtype, g.M, g.K)),
               "weight_gemm: LayerNorm / quantising prologue needs gamma / beta (LN) and an A "
               "image that fits LDS");
   const int kstep = g.dtype == LLM_I8 ? 64 : 32;
@@ -133,6 +176,7 @@ int llm::weight_gemm(const WeightGemm& g, hipStream_t st) {
   a.ln_x = g.ln_x; a.ln_eps = g.ln_eps;
   a.ln_g = g.ln_quant_only ? nullptr : g.ln_g;
   a.ln_b = g.ln_quant_only ? nullptr : g.ln_b;
+  a.ln_rms = g.ln_x && !g.ln_quant_only && g.ln_norm == LLM_NORM_RMS;
   a.ln_emb = g.ln_emb; a.ln_tok = g.ln_tok; a.ln_V = g.ln_V;
   a.act_out = static_cast<uint8_t*>(g.act_out);
   a.sa_out = g.sa_out;

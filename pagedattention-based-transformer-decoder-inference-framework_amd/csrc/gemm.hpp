@@ -60,6 +60,9 @@ struct WeightGemm {
   const float* ln_g = nullptr;
   const float* ln_b = nullptr;
   float ln_eps = 1e-5f;
+  // LLM_NORM_LAYER, or LLM_NORM_RMS: the prologue is RMSNorm (ln_b unused, may
+  // be NULL), a kernel instantiation of its own
+  int ln_norm = LLM_NORM_LAYER;
   void* act_out = nullptr;
   float* sa_out = nullptr;
   int w_keep = 0;  // weights with the default cache policy (kept in the Infinity Cache), else nt

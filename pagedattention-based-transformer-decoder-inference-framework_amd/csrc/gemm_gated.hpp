@@ -36,10 +36,21 @@ struct GatedGemm {
   int32_t* acc_gate = nullptr;
   int32_t* acc_up = nullptr;
   int w_keep = 0;  // weights with the default cache policy, else nt (WeightGemm::w_keep)
+  // RMSNorm prologue (gated_rms_fusable rows only): A = RMSNorm(ln_x) with
+  // ln_g / ln_eps, built per workgroup in LDS (I8: quantised per row, the row
+  // scales replace sa); A / lda / a_packed / sa are then ignored.  act_out /
+  // sa_out optionally receive the image (packed-A order) and the row scales.
+  const float* ln_x = nullptr;
+  const float* ln_g = nullptr;
+  float ln_eps = 1e-5f;
+  void* act_out = nullptr;
+  float* sa_out = nullptr;
 };
 
 // `who` names the entry in error messages.  Every check runs on the host
 // before the launch.
 int gated_gemm(const GatedGemm& g, hipStream_t st, const char* who = "gated_gemm");
+// Whether gated_gemm can run the RMSNorm prologue for M rows of K into N columns.
+bool gated_rms_fusable(int dtype, int M, int N, int K);
 
 }  // namespace llm

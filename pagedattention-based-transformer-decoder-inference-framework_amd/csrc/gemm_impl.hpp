@@ -111,6 +111,9 @@ struct GemmArgs {
   int seam_n;
   int qdiag;  // tuning build, timing only: bit0 skip the prologue, bit1 no weight loads before it
   int ksplit2;  // WeightGemm::ksplit2: gridDim.z = 2, each slice atomically adds into C
+  // 1: the prologue is RMSNorm (gemm_kernel<..., PRO = 2>; ln_b unused), an
+  // instantiation of its own: every other launch runs the code it ran before
+  int ln_rms;
 };
 
 // LDS image of A for the LayerNorm prologue: row-major 16-byte groups, row
@@ -174,7 +177,8 @@ struct GemmTraits<GemmKind::F16> {
 // the LDS image of A (ln_row_stride) and, for I8, the row scales into sa_lds:
 // ln_wave.hpp, bit-identical to the LayerNorm launch.  One wave per row (rows
 // w, w + WAVES, ...), two rows' loads in flight; gamma / beta loaded once.
-template <GemmKind KIND, int ROWS, int WAVES>
+// RMS: RMSNorm in LayerNorm's place (rms_wave_compute; beta is not loaded).
+template <GemmKind KIND, int ROWS, int WAVES, bool RMS = false>
 __device__ __forceinline__ void ln_prologue(const GemmArgs& a, int m0, uint8_t* alds,
                                             float* sa_lds) {
   constexpr int ESIZE = GemmTraits<KIND>::ESIZE;
@@ -187,9 +191,10 @@ __device__ __forceinline__ void ln_prologue(const GemmArgs& a, int m0, uint8_t* 
   // ln_g == NULL: quantise only (I8: the fp32 rows are the attention output,
   // the o_proj prologue replacing the merge launch's per-row quantisation)
   const bool do_ln = a.ln_g != nullptr;
-  LnRow<CPL> gm, bt;
+  LnRow<CPL> gm;
+  LnRow<RMS ? 1 : CPL> bt;
   ln_wave_load(a.ln_g, K4, do_ln, gm);
-  ln_wave_load(a.ln_b, K4, do_ln, bt);
+  if constexpr (!RMS) ln_wave_load(a.ln_b, K4, do_ln, bt);
   for (int r0 = w; r0 < ROWS; r0 += 2 * WAVES) {
     LnRow<CPL> x[2];
 #pragma unroll
@@ -209,7 +214,9 @@ __device__ __forceinline__ void ln_prologue(const GemmArgs& a, int m0, uint8_t* 
       if (r >= ROWS) break;
       const bool mok = m0 + r < a.M;  // rows past M: zero A (their outputs are not stored)
       float am;
-      if (do_ln) {
+      if constexpr (RMS) {
+        am = rms_wave_compute(x[q], gm, K, a.ln_eps);
+      } else if (do_ln) {
         am = ln_wave_compute(x[q], gm, bt, K, a.ln_eps);
       } else {
         am = 0.f;
@@ -449,7 +456,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int bx, int by, int
 #if LLM_TUNING
     if ((a.qdiag & 1) == 0)
 #endif
-    ln_prologue<KIND, ROWS_, WAVES>(a, m0, alds, sa_lds);
+    ln_prologue<KIND, ROWS_, WAVES, PRO == 2>(a, m0, alds, sa_lds);
     __syncthreads();
     if constexpr (KIND == GemmKind::I8) {
 #pragma unroll
@@ -688,6 +695,10 @@ hipError_t launch_gemm_form(const GemmArgs& a, const GemmForm& f, dim3 grid, hip
   if constexpr (NT <= 2) {
     if (f.prologue) {
       const size_t lds = ln_lds_bytes<KIND, MT, NT, 8>(a.K);
+      if (a.ln_rms) {
+        hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 2, ROPE>), grid, dim3(512), lds, st, a);
+        return hipGetLastError();
+      }
       hipLaunchKernelGGL((gemm_kernel<KIND, MT, NT, 8, 0, 1, ROPE>), grid, dim3(512), lds, st, a);
       return hipGetLastError();
     }

@@ -162,6 +162,36 @@ __device__ __forceinline__ float ln_wave_compute(LnRow<CPL>& x, const LnRow<CPL>
   return ln_wave_max(am);
 }
 
+// x -> RMSNorm(x) in place (include/llm_decoder.h, "RMSNorm"); returns the
+// row's |max| (wave-uniform).  One reduction: the mean of squares, fmaf
+// partials in the RMS launch's order (row_ops.hip rmsnorm_rows_kernel: lane l's
+// chunk j = w + 4 i is chunk i of launch thread 64 w + l), so the bits are the
+// launch's.  Chunks past the row hold zeros: fmaf(0, 0, p) = p and y = 0.
+template <int CPL>
+__device__ __forceinline__ float rms_wave_compute(LnRow<CPL>& x, const LnRow<CPL>& gm, int K,
+                                                  float eps) {
+  float p[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    p[w] = 0.f;
+#pragma unroll
+    for (int i = 0; w + 4 * i < CPL; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) p[w] = fmaf(x.v[w + 4 * i][e], x.v[w + 4 * i][e], p[w]);
+  }
+  const float ms = ln_row_sum(p) / (float)K;
+  const float inv_rms = (float)(1.0 / (double)sqrtf(ms + eps));
+  float am = 0.f;
+#pragma unroll
+  for (int j = 0; j < CPL; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      x.v[j][e] = __fmul_rn(__fmul_rn(x.v[j][e], inv_rms), gm.v[j][e]);
+      am = fmaxf(am, fabsf(x.v[j][e]));
+    }
+  return ln_wave_max(am);
+}
+
 // 4 values -> 4 int8 in one dword (int8_quant.cpp quantize_to_int8 semantics)
 __device__ __forceinline__ uint32_t ln_quant4(f32x4 y, float scale) {
   uint32_t wd = 0;

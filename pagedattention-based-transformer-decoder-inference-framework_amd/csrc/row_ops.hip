@@ -263,6 +263,108 @@ __global__ __launch_bounds__(kRowThreads) void layernorm_rows_kernel(
   if (q && threadIdx.x == 0) inv_scale[r] = 1.0f / scale;
 }
 
+// RMSNorm (+ int8 quantisation) launch (include/llm_decoder.h, "RMSNorm"):
+// layernorm_rows_kernel's shape -- one workgroup per row, VPT float4 chunks per
+// thread in one round trip, packed outputs -- with ONE reduction, the sum of
+// squares, and no beta.  ln_wave.hpp rms_wave_compute (the GEMM prologues)
+// follows this kernel's summation order: change one and the other must follow.
+template <int VPT>
+__global__ __launch_bounds__(kRowThreads) void rmsnorm_rows_kernel(
+    const float* x /* not restrict: pp.zero_x may point at it */, int rows, int cols,
+    const float* __restrict__ gamma, float eps, float* __restrict__ out, int8_t* __restrict__ q,
+    float* __restrict__ inv_scale, _Float16* __restrict__ out16, int pack, LnSource pp) {
+  __shared__ float sh[4];
+  const int r = blockIdx.x;
+  const int n4 = cols >> 2;
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(gamma);
+  f32x4 v[VPT], gv[VPT];
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  const h4* er = pp.emb ? reinterpret_cast<const h4*>(ln_embed_row(pp.emb, pp.tok, r, pp.V, cols))
+                        : nullptr;
+  const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)r * cols);
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    const int c = threadIdx.x + i * kRowThreads;
+    const bool ok = c < n4;
+    if (er) {
+      const h4 e = ok ? er[c] : h4{0, 0, 0, 0};
+      v[i] = f32x4{(float)e[0], (float)e[1], (float)e[2], (float)e[3]};
+    } else {
+      v[i] = ok ? xr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    gv[i] = ok ? g4[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s = fmaf(v[i][e], v[i][e], s);  // chunks past the row add 0
+  const float ms = block_sum_fast(s, sh) / (float)cols;
+  if (pp.zero_x && !pp.emb) {  // (after the barrier in block_sum_fast: every thread's loads are done)
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int c = threadIdx.x + i * kRowThreads;
+      if (c < n4) reinterpret_cast<f32x4*>(pp.zero_x + (size_t)r * cols)[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  const float inv_rms = (float)(1.0 / (double)sqrtf(ms + eps));
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[i][e] = __fmul_rn(__fmul_rn(v[i][e], inv_rms), gv[i][e]);
+      am = fmaxf(am, fabsf(v[i][e]));
+    }
+  const float scale = q ? 127.f / (block_max_fast(am, sh) + 1e-6f) : 1.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    const int c = threadIdx.x + i * kRowThreads;
+    if (c >= n4) continue;
+    const int k = 4 * c;
+    if (out) reinterpret_cast<f32x4*>(out + (size_t)r * cols)[c] = v[i];
+    if (q)
+      *reinterpret_cast<uint32_t*>(q + (pack ? a_frag_off_i8(r, k, cols >> 6) : (size_t)r * cols + k)) =
+          ln_quant4(v[i], scale);
+    if (out16)
+      *reinterpret_cast<ln_f16x4*>(out16 + (pack ? a_frag_off_f16(r, k, cols >> 5) : (size_t)r * cols + k)) =
+          ln_half4(v[i]);
+  }
+  if (q && threadIdx.x == 0) inv_scale[r] = 1.0f / scale;
+}
+
+// Widths that are no multiple of 4 (C ABI only): layernorm_quant_kernel's
+// shape, the row kept in dynamic LDS.
+__global__ __launch_bounds__(kRowThreads) void rmsnorm_quant_kernel(
+    const float* __restrict__ x, int cols, const float* __restrict__ gamma, float eps,
+    float* __restrict__ out, int8_t* __restrict__ q, float* __restrict__ inv_scale) {
+  extern __shared__ __attribute__((aligned(16))) float row[];  // cols floats
+  __shared__ float sh[kRowThreads / 64];
+  const int r = blockIdx.x;
+  const float* xr = x + (size_t)r * cols;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < cols; i += blockDim.x) {
+    const float v = xr[i];
+    row[i] = v;
+    s = fmaf(v, v, s);
+  }
+  const float ms = block_reduce_sum(s, sh) / (float)cols;
+  const float inv_rms = (float)(1.0 / (double)sqrtf(ms + eps));
+  float am = 0.f;
+  for (int i = threadIdx.x; i < cols; i += blockDim.x) {
+    const float y = __fmul_rn(__fmul_rn(row[i], inv_rms), gamma[i]);
+    row[i] = y;
+    am = fmaxf(am, fabsf(y));
+    if (out) out[(size_t)r * cols + i] = y;
+  }
+  if (q) {
+    am = block_reduce_max(am, sh);
+    const float scale = 127.f / (am + 1e-6f);
+    for (int i = threadIdx.x; i < cols; i += blockDim.x) q[(size_t)r * cols + i] = quant1(row[i], scale);
+    if (threadIdx.x == 0) inv_scale[r] = 1.0f / scale;
+  }
+}
+
 // VPT (float4 chunks per thread) for a row of `cols`; 0 = use the scalar kernel.
 static int row_vpt(int cols) {
   if (cols % 4 != 0) return 0;
@@ -467,6 +569,30 @@ hipError_t launch_layernorm_f16(const float* x, int rows, int cols, const float*
                    static_cast<_Float16*>(out16), st, pack, pp);
 }
 
+hipError_t launch_rmsnorm(const float* x, int rows, int cols, const float* g, float eps, float* out,
+                          int8_t* q, float* inv, void* out16, hipStream_t st, int pack,
+                          const LnSource* pp) {
+  const LnSource none{};
+  const int v = row_vpt(cols);
+  if (pack && (v == 0 || cols % 64 != 0)) return hipErrorInvalidValue;
+  if (v == 0) {  // odd widths (C ABI only): fp32 / row-major int8 from x rows
+    if (out16 || (pp && pp->emb)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rmsnorm_quant_kernel, dim3(rows), dim3(kRowThreads),
+                       (size_t)cols * sizeof(float), st, x, cols, g, eps, out, q, inv);
+    return hipGetLastError();
+  }
+  const dim3 gr(rows), bl(kRowThreads);
+#define RMS_CASE(V)                                                                            \
+  if (v == V) {                                                                                \
+    hipLaunchKernelGGL((rmsnorm_rows_kernel<V>), gr, bl, 0, st, x, rows, cols, g, eps, out, q, \
+                       inv, static_cast<_Float16*>(out16), pack, pp ? *pp : none);             \
+    return hipGetLastError();                                                                  \
+  }
+  RMS_CASE(1) RMS_CASE(2) RMS_CASE(4) RMS_CASE(8) RMS_CASE(16)
+#undef RMS_CASE
+  return hipErrorInvalidValue;
+}
+
 hipError_t launch_to_f16(const float* x, size_t n, void* y, hipStream_t st, int pack_cols) {
   if (n == 0) return hipSuccess;
   if (pack_cols > 0 && pack_cols % 32 != 0) return hipErrorInvalidValue;
@@ -555,6 +681,20 @@ extern "C" int layernorm_quant(const float* x, int rows, int cols, const float* 
   LLM_REQUIRE(cols <= 16384, "layernorm_quant: cols > 16384 (LDS row buffer)");
   LLM_HIP_RET(launch_layernorm_quant(x, rows, cols, gamma, beta, eps, out, q, inv_scale,
                                      as_stream(stream), 0));
+  return LLM_OK;
+}
+
+extern "C" int rmsnorm_quant(const float* x, int rows, int cols, const float* gamma, float eps,
+                             float* out, int8_t* q, float* inv_scale, void* stream) {
+  LLM_REQUIRE(rows >= 0 && cols > 0, "rmsnorm_quant: bad shape");
+  LLM_REQUIRE(eps > 0.f, "rmsnorm_quant: eps must be > 0");
+  if (rows == 0) return LLM_OK;
+  LLM_REQUIRE(x && gamma, "rmsnorm_quant: NULL pointer");
+  LLM_REQUIRE((q == nullptr) == (inv_scale == nullptr), "rmsnorm_quant: q and inv_scale go together");
+  LLM_REQUIRE(out || q, "rmsnorm_quant: no output requested");
+  LLM_REQUIRE(cols <= 16384, "rmsnorm_quant: cols > 16384 (LDS row buffer)");
+  LLM_HIP_RET(launch_rmsnorm(x, rows, cols, gamma, eps, out, q, inv_scale, nullptr,
+                             as_stream(stream), 0));
   return LLM_OK;
 }
 

@@ -21,6 +21,11 @@ hipError_t launch_layernorm_quant(const float* x, int rows, int cols, const floa
 hipError_t launch_layernorm_f16(const float* x, int rows, int cols, const float* g,
                                 const float* b, float eps, void* out16, hipStream_t st,
                                 int pack = 0, const LnSource* pp = nullptr);
+// RMSNorm rows (include/llm_decoder.h, "RMSNorm"): any of fp32 out, int8 q +
+// inv (row scales) and fp16 out16; pack / pp as the LayerNorm launches.
+hipError_t launch_rmsnorm(const float* x, int rows, int cols, const float* g, float eps, float* out,
+                          int8_t* q, float* inv, void* out16, hipStream_t st, int pack = 0,
+                          const LnSource* pp = nullptr);
 hipError_t launch_to_f16(const float* x, size_t n, void* y, hipStream_t st, int pack_cols = 0);
 hipError_t launch_advance(int32_t* pos, int32_t* ctx, int n, hipStream_t st);
 hipError_t launch_argmax(const float* logits, int rows, int V, int32_t* out, int32_t* out2,

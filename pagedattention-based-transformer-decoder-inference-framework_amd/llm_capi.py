@@ -225,6 +225,19 @@ _SIGS = {
     "llm_decoder_set_mlp": (c_int, [c_void_p, c_int]),
     "llm_decoder_mlp": (c_int, [c_void_p]),
     "llm_decoder_set_up_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    # RMSNorm (include/llm_decoder.h "RMSNorm"): row launch, GEMM prologues, decoder mode
+    "rmsnorm_quant": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
+    "i8_gemm_rms": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "f16_gemm_rms": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_void_p, c_int, c_void_p, c_void_p]),
+    "i8_gemm_gated_rms": (c_int, [c_void_p, c_void_p, c_float] + [c_void_p] * 6 + [c_int] * 3 +
+                          [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
+    "f16_gemm_gated_rms": (c_int, [c_void_p, c_void_p, c_float] + [c_void_p] * 4 + [c_int] * 3 +
+                           [c_void_p] * 2 + [c_int] + [c_void_p] * 2),
+    "llm_decoder_set_norm": (c_int, [c_void_p, c_int, c_float]),
+    "llm_decoder_norm": (c_int, [c_void_p]),
     # INT4 weights (csrc/gemm_w4.hip, csrc/w4_quant.cpp)
     "w4_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "w4_expand": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -1156,6 +1169,69 @@ def layernorm_quant(x, gamma, beta, eps=1e-5, quant=True, stream=None):
     check(lib.layernorm_quant(ptr(x), R, C, ptr(gamma), ptr(beta), eps, ptr(out), ptr(q), ptr(s),
                               stream_ptr(stream)))
     return out, q, s
+
+
+def rmsnorm_quant(x, gamma, eps=1e-5, quant=True, stream=None):
+    """rmsnorm_quant over device tensors: (out fp32, q int8, inv_scale) of x [R][C]."""
+    import torch
+    lib = load()
+    R, C = x.shape
+    out = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    q = torch.empty((R, C), dtype=torch.int8, device=x.device) if quant else None
+    s = torch.empty(R, dtype=torch.float32, device=x.device) if quant else None
+    check(lib.rmsnorm_quant(ptr(x), R, C, ptr(gamma), eps, ptr(out), ptr(q), ptr(s),
+                            stream_ptr(stream)))
+    return out, q, s
+
+
+def _packed_a(M, K, f16, dev):
+    """Zeroed flat tensor for M rows of K in packed-A order (whole 16-row tiles)."""
+    import torch
+    n = (M + 15) // 16 * 16 * K
+    return torch.zeros(n, dtype=torch.float16 if f16 else torch.int8, device=dev)
+
+
+def gemm_rms(x, gamma, W_packed, N, *, f16=False, eps=1e-5, sw=None, bias=None, act=0, stream=None):
+    """i8_gemm_rms / f16_gemm_rms (f16) over device tensors: returns (C, a_out,
+    sa_out) -- C fp32 [M][N], the prologue's image as a flat packed-A tensor and
+    the I8 row scales (None for fp16)."""
+    import torch
+    lib = load()
+    M, K = x.shape
+    C = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    a = _packed_a(M, K, f16, x.device)
+    if f16:
+        check(lib.f16_gemm_rms(ptr(x), ptr(gamma), eps, ptr(W_packed), ptr(C), M, N, K, ptr(bias),
+                               act, ptr(a), stream_ptr(stream)))
+        return C, a, None
+    s = torch.empty(M, dtype=torch.float32, device=x.device)
+    check(lib.i8_gemm_rms(ptr(x), ptr(gamma), eps, ptr(W_packed), ptr(C), M, N, K, ptr(sw),
+                          ptr(bias), act, ptr(a), ptr(s), stream_ptr(stream)))
+    return C, a, s
+
+
+def gemm_gated_rms(x, gamma, Wg_packed, Wu_packed, N, *, f16=False, eps=1e-5, sw_gate=None,
+                   sw_up=None, b_gate=None, b_up=None, mlp=LLM_MLP_GATED_SILU, stream=None):
+    """i8_gemm_gated_rms / f16_gemm_gated_rms (f16) over device tensors: returns
+    (acc_gate, acc_up, H, a_out, sa_out); the sums and scales are None for fp16."""
+    import torch
+    lib = load()
+    M, K = x.shape
+    dev = x.device
+    H = torch.empty((M, N), dtype=torch.float32, device=dev)
+    a = _packed_a(M, K, f16, dev)
+    if f16:
+        check(lib.f16_gemm_gated_rms(ptr(x), ptr(gamma), eps, ptr(Wg_packed), ptr(Wu_packed),
+                                     ptr(H), None, M, N, K, ptr(b_gate), ptr(b_up), mlp, ptr(a),
+                                     stream_ptr(stream)))
+        return None, None, H, a, None
+    ag = torch.empty((M, N), dtype=torch.int32, device=dev)
+    au = torch.empty((M, N), dtype=torch.int32, device=dev)
+    s = torch.empty(M, dtype=torch.float32, device=dev)
+    check(lib.i8_gemm_gated_rms(ptr(x), ptr(gamma), eps, ptr(Wg_packed), ptr(Wu_packed), ptr(ag),
+                                ptr(au), ptr(H), None, M, N, K, ptr(sw_gate), ptr(sw_up),
+                                ptr(b_gate), ptr(b_up), mlp, ptr(a), ptr(s), stream_ptr(stream)))
+    return ag, au, H, a, s
 
 
 def rope_table(theta: float, head_dim: int, num_pos: int):
